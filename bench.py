@@ -13,7 +13,13 @@ steps.  Multi-GPU: one process per GPU (torch.distributed.run); each rank owns
 its own shard of nodes of a weak-scaled cluster (5,000 nodes per GPU) —
 see DESIGN.md "Multi-GPU".
 
-The same JSON line also carries the other BASELINE configs as extra keys
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--dump-outputs DIR also writes what the last timed step computed (the per-pod
+results a caller of the queue path reads back) as DIR/<name>.npy.  Everything
+else is behind --full: the sampled roofline pass, the drop-in latency, the CPU
+baselines and the other configs.
+
+With --full the same JSON line also carries the other BASELINE configs as extra keys
 (--extra): cfg3 and cfg4 queues at full size, and cfg5 — one what-if step of
 4,096 pods x 1,000,000 nodes per timed step (bench_whatif.py) — each with its own
 roofline (and, at N=1, its CPU baseline).  At N>1 they run node-sharded over the
@@ -41,6 +47,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--nodes", type=int, default=5000)
     ap.add_argument("--pods", type=int, default=10000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's per-pod results "
+                    "(selected, feasible, status, total) as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true", help="beside the headline: the sampled roofline pass, the drop-in "
+                    "latency, the CPU baselines and the other configs (the options below apply only with --full)")
     ap.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU oracle on a bounded sample (rank 0, N=1)")
     ap.add_argument("--cpu-seconds", type=float, default=4.0, help="CPU time per oracle variant")
     ap.add_argument("--extra", default="3,4,5", help="other BASELINE configs reported beside cfg2 (node-sharded "
@@ -357,6 +367,43 @@ def parse_sizes(spec):
     return out
 
 
+def dump_outputs(path, res):
+    """--dump-outputs: the per-pod results of the last timed step (what ksg_pod_results
+    hands a caller of the queue path), one float64 array of queue length per field."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name in ("selected", "feasible", "status", "total"):
+        np.save(os.path.join(path, name + ".npy"), np.array([getattr(r, name) for r in res], dtype=np.float64))
+
+
+def headline_roofline(s, world, shard):
+    """--full: the cfg2 roofline from one more, sampled step after the timed region."""
+    n_pods = s.queue_len
+    wr0 = s.window_runs()
+    kernel_ms, kcount = sample_dominant(s, 64)
+    persistent = s.window_runs() > wr0  # one k_window_run launch for the whole queue
+    nwin = (n_pods + WINDOW - 1) // WINDOW
+    if persistent:
+        kernel_ms /= nwin  # per window inside the persistent launch
+    if s.batch_path:
+        kname = "k_window_run" if persistent else "k_window"
+        bytes_per_launch = window_bytes_per_launch(shard)
+    else:
+        kname = "k_filter_score"
+        bytes_per_launch = shard * algorithmic_bytes_per_node_fit_ba()
+    achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
+    traffic = pmc_traffic(kname) if world == 1 else None
+    if persistent and traffic is not None:
+        traffic /= nwin  # (the PMC pass counts the whole-queue launch: per window, like bytes_per_launch)
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "kernel": kname, "kernel_avg_us": kernel_ms * 1e3, "kernel_samples": kcount,
+            "bytes_per_launch": bytes_per_launch,
+            **({"note": "k_window_run: the whole queue in one persistent launch; kernel_avg_us and "
+                        "bytes_per_launch per 32-pod window inside it (launch time / windows)",
+                "windows_per_launch": nwin} if persistent else {})}
+
+
 def main():
     a = parse()
     rank = int(os.environ.get("RANK", 0))
@@ -385,29 +432,18 @@ def run(a, torch, rank=0, world=1, local=0, dist=None):
     s.load_cluster(doc)
     n_nodes, n_pods = s.n_nodes, s.queue_len  # n_nodes: whole cluster
     elapsed = time_queue(s, torch, a.steps, a.warmup, dist)
-    wr0 = s.window_runs()
-    kernel_ms, kcount = sample_dominant(s, 64)
-    persistent = s.window_runs() > wr0  # one k_window_run launch for the whole queue
-    nwin = (n_pods + WINDOW - 1) // WINDOW
-    if persistent:
-        kernel_ms /= nwin  # per window inside the persistent launch
-    res = s.results()
-    dropin = dropin_latency(s, doc) if world == 1 else None
+    res = s.results()  # what the last timed step computed
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res)
     scheduled = sum(1 for r in res if r.status == 0)
     pairs = float(n_nodes) * n_pods * a.steps  # n_nodes already spans all ranks
     value = pairs / elapsed
     ms_per_step = elapsed * 1e3 / a.steps
     shard = n_nodes // world
-    if s.batch_path:
-        kname = "k_window_run" if persistent else "k_window"
-        bytes_per_launch = window_bytes_per_launch(shard)
-    else:
-        kname = "k_filter_score"
-        bytes_per_launch = shard * algorithmic_bytes_per_node_fit_ba()
-    achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
-    traffic = pmc_traffic(kname) if world == 1 else None
-    if persistent and traffic is not None:
-        traffic /= nwin  # (the PMC pass counts the whole-queue launch: per window, like bytes_per_launch)
+    roofline = dropin = None
+    if a.full:
+        roofline = headline_roofline(s, world, shard)
+        dropin = dropin_latency(s, doc) if world == 1 else None
     del s
     out = None
     if rank == 0:
@@ -429,18 +465,15 @@ def run(a, torch, rank=0, world=1, local=0, dist=None):
                        "parallelism": f"node-shard x{world} (RCCL all-gather per 32-pod batch)" if world > 1 else "1 GPU",
                        **({"transport": "rccl"} if world > 1 else {})},
             "scheduled_pods_per_s": scheduled * a.steps / elapsed,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": kname, "kernel_avg_us": kernel_ms * 1e3, "kernel_samples": kcount,
-                         "bytes_per_launch": bytes_per_launch,
-                         **({"note": "k_window_run: the whole queue in one persistent launch; kernel_avg_us and "
-                                     "bytes_per_launch per 32-pod window inside it (launch time / windows)",
-                             "windows_per_launch": nwin} if persistent else {})},
         }
+        if roofline:
+            out["roofline"] = roofline
         if dropin:
             out["dropin"] = dropin
-        if a.cpu_baseline and world == 1:
+        if a.full and a.cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(json.dumps(doc).encode(), n_nodes, a.cpu_workers, a.cpu_seconds, "cfg2")
+    if not a.full:
+        return out
     # the other BASELINE configs: one GPU, or node-sharded over every rank (each
     # rank runs every leg: the exchanges are collective)
     sizes = parse_sizes(a.extra_sizes)

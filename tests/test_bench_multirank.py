@@ -1,7 +1,7 @@
 """bench.py's multi-GPU line, on the CPU: two ranks over gloo, the engine stubbed.
 
 The driver's SCALE run launches `bench.py --gpus N` as N processes over RCCL; this
-test runs the same `bench.run` at world size 2 with a gloo process group and a
+test runs the same `bench.run`, with `--full` for the sharded legs, at world size 2 with a gloo process group and a
 stand-in for the engine context, and checks that every rank runs every leg (the
 stand-in's schedule / what-if steps are collectives: a rank that skipped one
 would hang the other), that the line carries the sharded cfg3 / cfg4 / cfg5 legs
@@ -114,7 +114,7 @@ def _rank_main(rank, world, port, out_path):
     import bench
     torch.cuda.synchronize = lambda *a, **k: None  # (no GPU: the stand-in runs nothing)
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--nodes", "40", "--pods", "64",
-                "--extra-sizes", "3:90:64,4:120:48:200,5:400:32"]
+                "--full", "--extra-sizes", "3:90:64,4:120:48:200,5:400:32"]
     a = bench.parse()
     out = bench.run(a, torch, rank, world, 0, dist)
     if rank == 0:
@@ -124,6 +124,40 @@ def _rank_main(rank, world, port, out_path):
         assert out is None
     dist.barrier()
     dist.destroy_process_group()
+
+
+def test_plain_run_times_only_the_steps_and_dumps_outputs(tmp_path, monkeypatch):
+    """Without --full: warm-up + timed steps and nothing else on the engine (no sampled
+    pass, no drop-in cycles, no other config), the headline fields, and with
+    --dump-outputs the last step's per-pod results as float64 arrays."""
+    import numpy as np
+    import torch
+
+    class _NoDist:
+        def barrier(self):
+            pass
+
+    made = []
+    fake = _fake_ksg(0, 1, _NoDist())
+    mk = fake["ksg.distributed"].sharded_scheduler
+    fake["ksg.distributed"].sharded_scheduler = lambda *a: made.append(mk(*a)) or made[-1]
+    for k, v in fake.items():
+        monkeypatch.setitem(sys.modules, k, v)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    import bench
+    dump = tmp_path / "dump"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--nodes", "40",
+                                      "--pods", "64", "--dump-outputs", str(dump)])
+    d = bench.run(bench.parse(), torch)
+    assert len(made) == 1 and made[0].calls == 3 + 2
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d)
+    assert d["steps"] == 3 and d["value"] == pytest.approx(40 * 64 * 3 / (d["ms_per_step"] * 3 / 1e3))
+    assert not {"roofline", "dropin", "cpu_baseline", "cfg3", "cfg4", "cfg5"} & set(d)
+    assert sorted(p.name for p in dump.iterdir()) == ["feasible.npy", "selected.npy", "status.npy", "total.npy"]
+    for p in dump.iterdir():
+        x = np.load(p)
+        assert x.dtype == np.float64 and x.shape == (64,)
+    assert np.load(dump / "feasible.npy").tolist() == [1.0] * 64
 
 
 @pytest.mark.timeout(300)

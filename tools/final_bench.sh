@@ -11,6 +11,7 @@ if [ -z "$NO_TESTS" ]; then
   TAG=${TAG}_gputest LIMIT=${TEST_LIMIT:-900} bash tools/gpu_tests.sh || exit 1
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1 || { tail -20 gpurun_out/${TAG}_smoke.log; exit 1; }
 fi
+BENCH_ARGS="--full ${BENCH_ARGS}"  # the whole line: the summary below reads roofline, dropin and cfg3 / cfg4 / cfg5
 timeout -k 10 900 python -u bench.py ${BENCH_ARGS} > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || { tail -20 gpurun_out/${TAG}_bench.err; exit 1; }
 for c in ${DROPIN_CFGS-2 4}; do
   timeout -k 10 300 python tools/dropin_c.py --cfg $c --out gpurun_out/${TAG}_dropin.jsonl > /dev/null 2> gpurun_out/${TAG}_dropin.err || { tail -20 gpurun_out/${TAG}_dropin.err; exit 1; }

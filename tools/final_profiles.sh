@@ -10,6 +10,7 @@ set -o pipefail
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 R=${1:-r06}
+export OUT=${OUT:-profile_out}  # where headline_profile.sh puts the headline's line, trace and PMC passes
 bash tools/headline_profile.sh $R > gpurun_out/${R}_headline.log 2>&1 || { tail -20 gpurun_out/${R}_headline.log; exit 1; }
 bash tools/pmc_config.sh 3 $R > gpurun_out/${R}_pmc3.log 2>&1 || { tail -20 gpurun_out/${R}_pmc3.log; exit 1; }
 bash tools/pmc_config.sh 4 $R > gpurun_out/${R}_pmc4.log 2>&1 || { tail -20 gpurun_out/${R}_pmc4.log; exit 1; }

@@ -2,7 +2,7 @@
 # GPU box A/B runner (replaces round 4's one-off tools/r04_gpu_*.sh recipes).
 #
 #   TAG=r05x ARMS="a:KSG_LIB=kube-scheduler-simulator-p9_amd/libksg.so b:KSG_LIB=kube-scheduler-simulator-p9_amd/libksg_b.so" \
-#   BENCH="python bench.py --extra '' --cpu-baseline 0 --steps 10 --warmup 2" REPS=2 \
+#   BENCH="python bench.py --full --extra '' --cpu-baseline 0 --steps 10 --warmup 2" REPS=2 \
 #   PARITY="tests/test_parity_gpu.py -k cfg2_large" PARITY_ARM=b bash tools/gpu_ab.sh
 #
 # ARMS   space-separated "name:VAR=value[,VAR=value...]" (the environment of each arm;
@@ -16,7 +16,7 @@ set -o pipefail
 mkdir -p gpurun_out
 TAG=${TAG:-ab}
 REPS=${REPS:-2}
-BENCH=${BENCH:-python bench.py --extra '' --cpu-baseline 0 --steps 10 --warmup 2}
+BENCH=${BENCH:-python bench.py --full --extra '' --cpu-baseline 0 --steps 10 --warmup 2}
 FIELDS=${FIELDS:-"d['value'], d['roofline']['kernel_avg_us']"}
 arm_env() {  # "name:A=1,B=2" -> "A=1 B=2"
   echo "${1#*:}" | tr ',' ' '

@@ -9,6 +9,7 @@ rc=$?
 tail -5 gpurun_out/gputest.log
 [ $rc -ne 0 ] && exit $rc
 [ -n "$NO_BENCH" ] && exit 0
+BENCH_ARGS="--full ${BENCH_ARGS}"  # the whole line: roofline, drop-in, CPU baselines, cfg3 / cfg4 / cfg5
 timeout -k 10 300 python bench.py ${BENCH_ARGS} > gpurun_out/bench.log 2>&1
 rc=$?
 tail -3 gpurun_out/bench.log

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 export TMPDIR=/tmp
 cd "$ROOT" || exit 1
 mkdir -p gpurun_out
-ARGS="--steps 2 --warmup 1 --cpu-baseline 0"
+ARGS="--full --steps 2 --warmup 1 --cpu-baseline 0"
 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/ktrace -o run -- python3 bench.py $ARGS > gpurun_out/ktrace.log 2>&1 || exit 1
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -o run -- python3 bench.py $ARGS > gpurun_out/pmc_fetch.log 2>&1 || exit 1
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -o run -- python3 bench.py $ARGS > gpurun_out/pmc_write.log 2>&1 || exit 1
