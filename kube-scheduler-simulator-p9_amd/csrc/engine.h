@@ -276,9 +276,10 @@ class Engine {
   bool set_exchange(int mode, const void* nccl_id, uint32_t rank, uint32_t ranks, ExchangeFn fn, void* user,
                     std::string& err);
   uint32_t exchange_ranks() const;
-  // diagnostic: pods the per-pod runs sent down the table chain / the scanning chain /
-  // of the table-chain pods, those whose cycle was one launch (k_eval_solo)
-  // and persistent segments that fell back to the two-launch chain (out[6])
+  // diagnostic counters: out[0] pods the per-pod runs sent down the table chain, out[1] down the
+  // scanning chain, out[2] unused (one-launch cycles, removed: always 0), out[3] what-if pod chunks on
+  // the class path, out[4] table-chain pods of persistent segments, out[5] those segments, out[6]
+  // persistent launches that fell back (segments and window loops), out[7] persistent window loops run
   void path_counts(uint64_t out[8]) const;
   // An aborted persistent launch left the device state half-updated: the context
   // must be reloaded (host.cpp marks it broken); cleared by a reload.

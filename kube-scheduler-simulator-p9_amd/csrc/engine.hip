@@ -815,11 +815,6 @@ __global__ void k_init_summaries(ksg_pod_summary* sum, uint32_t count, DevProfil
   sum[i] = s;
 }
 
-// append_program's placement of one staged [PodLite | program] block.
-__global__ void k_place_program(const uint8_t* __restrict__ src, uint32_t bytes, uint8_t* dst, uint64_t* off_slot,
-                                uint64_t off, void* plite_slot, int32_t* prow_slot, int32_t row, ksg_pod_summary* sum,
-                                DevProfile F);
-
 __global__ void k_begin(DevCluster C, DevScratch S, const uint8_t* __restrict__ prog) {
   ProgView V = view(prog);
   uint32_t ntsc = (uint32_t)(V.h->n_tsc_filter + V.h->n_tsc_score);
@@ -2265,8 +2260,10 @@ __global__ __launch_bounds__(kBlock) void k_fs_static(DevCluster C, DevProfile F
 #define KSG_CAND 64        // candidates per pod: >= 2*KSG_BATCH (see above)
 #define KSG_TOPK 64
 #ifndef KSG_WIN_THREADS
-#define KSG_WIN_THREADS 1024  // (a build-time knob for A/B builds: 512 lifts the 128-VGPR cap)
+#define KSG_WIN_THREADS 1024
 #endif
+// (not a knob: the replay's lane maps in win_fixup are 1,024-thread maps)
+static_assert(KSG_WIN_THREADS == 1024, "the window replay's lane maps assume 1024-thread blocks");
 #define KSG_TILE KSG_WIN_THREADS  // nodes per eval block
 #define KSG_STASH_NPT 8    // eval tiles of up to this many nodes per thread hold their outputs in LDS
 #ifndef KSG_STAGE
@@ -2316,6 +2313,7 @@ struct PodLite {  // the fields of ksg_prog the Fit/BA evaluation reads (LDS-sta
 // staging block [PodLite | pad | program]: the program 16-byte aligned
 constexpr size_t kPlOff = (sizeof(PodLite) + 15) & ~(size_t)15;
 static_assert(sizeof(PodLite) % 4 == 0, "PodLite words");
+// append_program's placement of one staged [PodLite | program] block.
 __global__ void k_place_program(const uint8_t* __restrict__ src, uint32_t bytes, uint8_t* dst, uint64_t* off_slot,
                                 uint64_t off, void* plite_slot, int32_t* prow_slot, int32_t row, ksg_pod_summary* sum,
                                 DevProfile F) {
@@ -2351,13 +2349,7 @@ struct WinArgs {
   uint32_t e0, ne, T, npt, tile_len;  // T tiles of tile_len <= KSG_TILE * npt nodes per pod
   uint64_t* tile_top;    // [KSG_BATCH][T][KSG_TOPK] (window E's buffer)
   int32_t* tile_feas;    // [KSG_BATCH][T][3]
-  // defer: the eval blocks only store their tile lists; block 0 of the next
-  // launch merges them (window W's buffers below) and loads the candidates'
-  // rows from the node rows — the pod's merge leaves the evaluation's chain
-  uint32_t defer;
   uint32_t stash_npt;  // eval tiles of up to this many nodes per thread hold all outputs in LDS
-  const uint64_t* wtile_top;
-  const int32_t* wtile_feas;
   uint32_t* arrive;      // [KSG_BATCH] tile arrivals (reset by the last block)
   uint8_t* erec;         // candidate record of window E (kRecBytes)
   // fixup part: window W = queue pods [w0, w0 + nw)
@@ -3129,7 +3121,7 @@ __global__ __launch_bounds__(256) void k_whatif_rec2(DevCluster C, DevProfile F,
 // Nothing per pair reaches memory.
 #define KSG_WC_CLS 128
 #define KSG_WC_PODS 32
-#define KSG_WC_NPT 4   // default nodes per thread (KSG_WC_NPT=1|2|4; 4 since round 6: 18.1 vs 18.5 ms/step)
+constexpr int kWcNpt = 4;  // nodes per thread (1 and 2 were measured slower and removed: 18.1 vs 18.5 ms/step, round 6)
 #define KSG_WC_TILE 4096  // nodes per block
 
 // A pod of the class path, decoded once per step (k_wc_decode) into a fixed
@@ -4154,15 +4146,11 @@ __device__ __forceinline__ void win_eval(const DevCluster& C, const DevProfile& 
       __hip_atomic_store(A.tile_feas + ((size_t)b * A.T + tile) * 3 + lane, c, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (A.defer) {
-      if (lane == 0) wcount[16] = 0u;
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      uint32_t old = 0;
-      if (lane == 0) old = __hip_atomic_fetch_add(A.arrive + b * A.astride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      old = __builtin_amdgcn_readfirstlane(old);
-      if (lane == 0) wcount[16] = (!A.mblocks && old == A.T - 1) ? 1u : 0u;  // (slots 17..31 unused)
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    uint32_t old = 0;
+    if (lane == 0) old = __hip_atomic_fetch_add(A.arrive + b * A.astride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    old = __builtin_amdgcn_readfirstlane(old);
+    if (lane == 0) wcount[16] = (!A.mblocks && old == A.T - 1) ? 1u : 0u;  // (slots 17..31 unused)
   }
   auto flush_stash = [&]() {
     if (!stash_all && w != 0) return;
@@ -4347,7 +4335,7 @@ __device__ __forceinline__ void origin_rows(const DevCluster& C, const WinLDS& L
   } else {
     int p = (o - 64) >> 6, i = (o - 64) & 63;
     if (i < KSG_STAGE) start = L.row[p][i];
-    else if (A.defer || PER) load_row_p<PER>(C, (uint32_t)(L.key[p][i] & 0xFFFFFull) - C.goff, A.need_eph, start);
+    else if (PER) load_row_p<PER>(C, (uint32_t)(L.key[p][i] & 0xFFFFFull) - C.goff, A.need_eph, start);
     else start = rec_rows(A.wrec)[p * KSG_CAND + i];
     snap = start;
   }
@@ -4538,7 +4526,7 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
   constexpr int kRowW = (int)(sizeof(RowV) / 8), kPendW = (int)(sizeof(Pend) / 8);
   const uint64_t* keys = rec_keys(A.wrec);
   const uint64_t* rows = reinterpret_cast<const uint64_t*>(rec_rows(A.wrec));
-  const int nk = nb * KSG_CAND, nr = A.defer ? 0 : nb * KSG_STAGE * kRowW;
+  const int nk = nb * KSG_CAND, nr = nb * KSG_STAGE * kRowW;
   uint64_t kv[2], rv[6];
   // (persistent loop) the prior step the eval blocks did: thread = (pod, prior entry)
   const int ppb = tid >> 5, ppe = tid & 31;
@@ -4564,62 +4552,19 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
     const uint64_t pv = tid < KSG_BATCH * kPendW ? ldv<PER>(reinterpret_cast<const uint64_t*>(A.pprev) + tid) : 0;
     constexpr int kPodW = (int)(sizeof(PodLite) / 8);
     const uint64_t qv = tid < nb * kPodW ? reinterpret_cast<const uint64_t*>(A.plite + A.w0)[tid] : 0;
-    const int32_t fv = tid < nb && !A.defer ? ldv<PER>(reinterpret_cast<const int32_t*>(A.wrec) + tid) : 0;
+    const int32_t fv = tid < nb ? ldv<PER>(reinterpret_cast<const int32_t*>(A.wrec) + tid) : 0;
     int32_t aT = 0, aA = 0;
     int64_t m0 = -1, m1 = -1;
     if (STAT && tid < nb) {
-      if (!A.defer) {
-        aT = ldv<PER>(reinterpret_cast<const int32_t*>(A.wrec) + KSG_BATCH + tid);
-        aA = ldv<PER>(reinterpret_cast<const int32_t*>(A.wrec) + 2 * KSG_BATCH + tid);
-      }
+      aT = ldv<PER>(reinterpret_cast<const int32_t*>(A.wrec) + KSG_BATCH + tid);
+      aA = ldv<PER>(reinterpret_cast<const int32_t*>(A.wrec) + 2 * KSG_BATCH + tid);
       m0 = ldv<PER>(A.mpred + 2 * (A.w0 - A.first + tid));
       m1 = ldv<PER>(A.mpred + 2 * (A.w0 - A.first + tid) + 1);
     }
-    if (A.defer) {
-      // merge pod b's T tile lists (wave w: pods w and w+16) and sum its tile counts;
-      // the first 8 tiles' loads are issued together
 #pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int b = wave + 16 * k;
-        uint64_t v = 0;
-        int32_t c[3] = {0, 0, 0};
-        if (b < nb) {
-          const uint64_t* tsrc = A.wtile_top + (size_t)b * A.T * KSG_TOPK;
-          uint64_t tl[8];
-#pragma unroll
-          for (int t = 0; t < 8; ++t) tl[t] = (uint32_t)t < A.T ? tsrc[(size_t)t * KSG_TOPK + lane] : 0;
-          for (uint32_t t = lane; t < A.T; t += 64)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) c[j] += A.wtile_feas[((size_t)b * A.T + t) * 3 + j];
-          v = tl[0];
-#pragma unroll
-          for (int t = 1; t < 8; ++t)
-            if ((uint32_t)t < A.T) v = wave_merge_top(v, wave_reverse(tl[t]));
-#pragma unroll 1
-          for (uint32_t t = 8; t < A.T; ++t) v = wave_merge_top(v, wave_reverse(tsrc[(size_t)t * KSG_TOPK + lane]));
-#pragma unroll
-          for (int j = 0; j < 3; ++j) c[j] = wave_sum(c[j]);
-        }
-        kv[k] = v;
-        if (b < nb && lane == 0) {
-          L.feas[b] = c[0];
-          if (STAT) {
-            L.achT[b] = c[1];
-            L.achA[b] = c[2];
-          }
-        }
-        if (b < nb && lane < KSG_STAGE && v) {  // candidate rows of the staged ranks (window-start rows)
-          RowV rr;
-          load_row(C, (uint32_t)(v & 0xFFFFFull) - C.goff, A.need_eph, rr);
-          L.row[b][lane] = rr;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        int i = tid + k * KSG_WIN_THREADS;
-        kv[k] = i < nk ? ldv<PER>(keys + i) : 0;
-      }
+    for (int k = 0; k < 2; ++k) {
+      int i = tid + k * KSG_WIN_THREADS;
+      kv[k] = i < nk ? ldv<PER>(keys + i) : 0;
     }
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
@@ -4644,12 +4589,10 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
     }
     if (tid < np * kPendW) reinterpret_cast<uint64_t*>(L.prior)[tid] = pv;
     if (tid < nb * kPodW) reinterpret_cast<uint64_t*>(L.pod)[tid] = qv;
-    if (tid < nb && !A.defer) L.feas[tid] = fv;
+    if (tid < nb) L.feas[tid] = fv;
     if (STAT && tid < nb) {
-      if (!A.defer) {
-        L.achT[tid] = aT;
-        L.achA[tid] = aA;
-      }
+      L.achT[tid] = aT;
+      L.achA[tid] = aA;
       L.mt[tid] = m0;
       L.ma[tid] = m1;
       L.fbf[tid] = 0;
@@ -5246,7 +5189,6 @@ __global__ __launch_bounds__(KSG_WIN_THREADS) void k_window_run(DevCluster C, De
   WinArgs A = A0;
   A.abortw = abortw;
   A.spin = RC.spin;
-  A.defer = 0;
   if (blockIdx.x == 0) {
     WinLDS& L = *reinterpret_cast<WinLDS*>(lds_raw);
     L.nxt_ok = 0;
@@ -5401,6 +5343,11 @@ struct DBuf {
   }
 };
 
+// Engine::Impl::hverdict, the pinned host block of the persistent launches: word 0
+// is the handshake verdict, word kVerdictAbortWord Engine::sync's copy of the abort word
+constexpr size_t kVerdictBytes = 64;
+constexpr size_t kVerdictAbortWord = 8;
+static_assert((kVerdictAbortWord + 1) * sizeof(uint32_t) <= kVerdictBytes, "the abort word lies inside the verdict block");
 struct Engine::Impl {
   EngineConfig cfg;
   // node-shard exchange (sharded batch path)
@@ -5501,7 +5448,9 @@ struct Engine::Impl {
   int32_t max_tid = -1;     // largest taint id on a node (what-if class path: < 64)
   bool taint_dup = false;   // some node lists a taint twice
   bool cols_small = false;  // cpu / memory columns of every node (alloc, requested, non-zero) in (-2^45, 2^45)
-  int wc_npt = KSG_WC_NPT;  // what-if class path: nodes per thread (KSG_WC_NPT)
+  size_t wi_rec_mb = 40960;  // what-if: pass 1's records per chunk of pods (KSG_WHATIF_REC_MB; 0: pass 2 recomputes)
+  bool wi_classes = true;    // what-if: the class path where it applies (KSG_WHATIF_CLASSES=0: off)
+  bool wi_wide = false;      // what-if: the 64-bit record path always (KSG_WHATIF_WIDE; tests)
   int64_t max_na_sum = 0;   // largest preferred NodeAffinity weight sum of a program
   bool static_fits = true; // raw scores fit the record (taints per node < 4096, NodeAffinity weights < 2^20)
   DBuf<StaticRec> stat;   // static records of a chunk of pods [chunk][N]
@@ -5538,8 +5487,6 @@ struct Engine::Impl {
   DBuf<int32_t> cpi, cpst;
   DBuf<int64_t> cpm, cpm2;
   DBuf<EvalTotals> cetot;
-  DBuf<SoloCand> ccand;   // k_eval_solo: classes per block [cnblk][kChain]
-  int solo = 0;           // one-launch cycles (k_eval_solo): 0 off, 1 on (KSG_SOLO)
   int run_on = 1;         // persistent segments (k_chain_run): KSG_RUN=0 turns them off
   int run_bt = 256;       // k_chain_run threads per block (KSG_RUN_BT=256|512)
   uint32_t run_cap512 = 0;
@@ -5548,7 +5495,8 @@ struct Engine::Impl {
   DBuf<RunSync> rsync;    // k_chain_run's flag / handshake (zeroed per launch) and sticky abort word
   DBuf<uint64_t> rgran;   // k_chain_run's tagged granules: partial records [2 parities], then keys [2] (zeroed per launch)
   bool run_used = false;  // a persistent segment ran since the last sync (its abort word is checked)
-  uint32_t* hverdict = nullptr;  // pinned, coherent: the handshake verdict of the last segment (the host polls it)
+  uint32_t* hverdict = nullptr;  // pinned, coherent (kVerdictBytes): the handshake verdict of the last segment (the host
+                                 // polls it), and at kVerdictAbortWord Engine::sync's copy of the device abort word
   uint32_t run_lag = 0;          // diagnostic (KSG_RUN_LAG): committer delay per pod, s_sleep(127) rounds
   uint32_t run_need_extra = 0;   // diagnostic (KSG_RUN_NORES=1): a grid that can never be all resident
   uint32_t run_wait_us = 5000;   // handshake limit (KSG_RUN_WAIT_US)
@@ -5559,12 +5507,6 @@ struct Engine::Impl {
   bool unwaited = false;         // a state-changing launch was queued without a wait (Reserve's k_assume):
                                  // a failing synchronisation then leaves host mirror and device apart (lost)
   DBuf<WinSync> wsync;           // k_window_run's counters (zeroed per launch)
-  int final_pm = 1;              // k_final specialised for the Fit/BA/PTS/IPA plugin set (KSG_FINAL_PM=0: generic)
-  int view_slots_direct = 1;     // k_view: message slots into the host block as claimed (KSG_VIEW_SLOTS_DIRECT=0: last block copies)
-  int view_narrow = 1;           // k_view: PTS / IPA raw rows by the summary's range (KSG_VIEW_NARROW=0: 4 bytes)
-  int place_fused = 1;           // add_classes places the cycle's program in its upload (KSG_PLACE_FUSED=0: off)
-  int pc_agg = 1;                // k_pc_build counts few-domain slots per block (KSG_PC_AGG=0: per row)
-  int pc_prefetch = 1;           // k_pc_build reads the requirement keys' label columns up front (KSG_PC_PREFETCH=0: off)
   int win_run_on = 1;            // persistent window loop (k_window_run): KSG_WIN_RUN=0 turns it off
   int win_mblocks = 0;           // ... with dedicated merge blocks (KSG_WIN_MB=1; the last tile block merges: measured faster)
   int view_copy = 0;             // cycle view: 1 = the per-node arrays by a copy (KSG_VIEW_COPY), 0 = written by k_view
@@ -5587,7 +5529,6 @@ struct Engine::Impl {
   uint32_t cnblk = 0;
   DBuf<int32_t> knorm;    // normalized scores of one kept pod
   DBuf<uint8_t> vblk;     // device cycle view block (Engine::view)
-  DBuf<uint32_t> vdone;   // k_view's finished-block count (direct views)
   bool vblk_fresh = true;
   uint32_t vgen = 0;      // view generation (slot-table entries of older views count as empty)
   size_t prog_bytes = 0;  // used bytes of the program blob
@@ -5602,14 +5543,14 @@ struct Engine::Impl {
   bool any_eph_req = false;
   // speculative batch path
   bool batch_ok = false;     // profile of Fit / BA (/ Taint / NodeAffinity) plugins only
-  bool batch_static = false;
-  uint32_t stat_chunk_cap = 0;
+  bool batch_static = false;  // ... with Taint / NodeAffinity: static records per pod (k_static)
+  uint32_t stat_chunk_cap = 0;  // diagnostic: cap on the static chunk (pods, multiple of KSG_BATCH)
   uint32_t n_cus = 256;  // compute units of the device
   hipStream_t sstream = nullptr;  // low-priority side stream (static records of the window path)
   hipStream_t rstream = nullptr, xstream = nullptr;  // sharded windows: replay / exchange streams (run_batches_split)
   hipEvent_t xg[2] = {nullptr, nullptr}, xr[2] = {nullptr, nullptr}, xe[2] = {nullptr, nullptr}, xjoin = nullptr;
-  bool static_side = false;  // KSG_STATIC_SIDE=1: measured no faster (the windows slow down beside it)
-  hipEvent_t sev_ready[3] = {nullptr, nullptr, nullptr}, sev_free = nullptr;  // diagnostic: cap on the static chunk (pods, multiple of KSG_BATCH)  // ... with Taint / NodeAffinity: static records per pod (k_static)
+  // the side kernel beside the persistent loop (k_static_dec_run): its records done / the side stream free to start
+  hipEvent_t sev_ready = nullptr, sev_free = nullptr;
   DBuf<uint64_t> tile_top;
   DBuf<int32_t> tfeas, pend_n;
   DBuf<uint32_t> arrive;
@@ -5641,7 +5582,10 @@ struct Engine::Impl {
   std::vector<hipEvent_t> sev_st;  // ... and around the static-record launches (k_static) of the same run
   uint32_t n_st = 0;
   uint64_t stat_pods_sampled = 0;
-  uint64_t path_pods[6] = {0, 0, 0, 0, 0, 0};  // diagnostic: pods run by the table chain / the scanning chain / of the first, in one launch; what-if pod chunks on the class path; table-chain pods of persistent segments (k_chain_run) / those segments
+  // diagnostic counters (Engine::path_counts): [0] pods run by the table chain, [1] by the scanning chain,
+  // [2] unused (one-launch cycles, removed: always 0), [3] what-if pod chunks on the class path,
+  // [4] table-chain pods of persistent segments (k_chain_run), [5] those segments
+  uint64_t path_pods[6] = {0, 0, 0, 0, 0, 0};
   std::vector<Engine::KernelStat> stats;
 
   DevCluster cluster() const {
@@ -5726,7 +5670,7 @@ Engine::~Engine() {
   if (p_->apstage_ev) (void)hipEventDestroy(p_->apstage_ev);
   if (p_->ev0) (void)hipEventDestroy(p_->ev0);
   if (p_->ev1) (void)hipEventDestroy(p_->ev1);
-  for (hipEvent_t e : {p_->sev_ready[0], p_->sev_ready[1], p_->sev_ready[2], p_->sev_free})
+  for (hipEvent_t e : {p_->sev_ready, p_->sev_free})
     if (e) (void)hipEventDestroy(e);
   if (p_->sstream) (void)hipStreamDestroy(p_->sstream);
   for (hipEvent_t e : {p_->xg[0], p_->xg[1], p_->xr[0], p_->xr[1], p_->xe[0], p_->xe[1], p_->xjoin})
@@ -5741,19 +5685,12 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
   Impl& I = *p_;
   I.cfg = cfg;
   if (const char* e = std::getenv("KSG_FOLD_BLOCKS")) I.fold_blocks = (uint32_t)std::strtoul(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_SOLO")) I.solo = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_RUN")) I.run_on = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_RUN_BT")) I.run_bt = std::strtol(e, nullptr, 10) == 512 ? 512 : 256;
   if (const char* e = std::getenv("KSG_RUN_MIN")) I.run_min = std::max<uint32_t>(1, (uint32_t)std::strtoul(e, nullptr, 10));
   if (const char* e = std::getenv("KSG_RUN_LAG")) I.run_lag = std::min<uint32_t>(4096, (uint32_t)std::strtoul(e, nullptr, 10));
   if (const char* e = std::getenv("KSG_RUN_NORES")) I.run_need_extra = std::strtol(e, nullptr, 10) != 0 ? 1u : 0u;
   if (const char* e = std::getenv("KSG_WIN_RUN")) I.win_run_on = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_PC_PREFETCH")) I.pc_prefetch = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_PC_AGG")) I.pc_agg = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_PLACE_FUSED")) I.place_fused = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_VIEW_NARROW")) I.view_narrow = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_FINAL_PM")) I.final_pm = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_VIEW_SLOTS_DIRECT")) I.view_slots_direct = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_WIN_MB")) I.win_mblocks = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_WIN_PFIX")) I.win_pfix = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_WIN_SPLIT")) I.win_split = (int)std::strtol(e, nullptr, 10);
@@ -5763,7 +5700,9 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
   if (const char* e = std::getenv("KSG_RUN_SPIN")) I.run_spin = std::max<uint32_t>(1, (uint32_t)std::strtoul(e, nullptr, 10));
   if (const char* e = std::getenv("KSG_RUN_WAIT_US"))
     I.run_wait_us = std::max<uint32_t>(10, std::min<uint32_t>(1000000, (uint32_t)std::strtoul(e, nullptr, 10)));
-  if (const char* e = std::getenv("KSG_WC_NPT")) I.wc_npt = (int)std::strtol(e, nullptr, 10);
+  if (const char* e = std::getenv("KSG_WHATIF_REC_MB")) I.wi_rec_mb = (size_t)std::strtoull(e, nullptr, 10);
+  if (const char* e = std::getenv("KSG_WHATIF_CLASSES")) I.wi_classes = std::strtol(e, nullptr, 10) != 0;
+  I.wi_wide = std::getenv("KSG_WHATIF_WIDE") != nullptr;
   if (const char* e = std::getenv("KSG_OCC_BLOCKS")) {
     I.occ_blocks = (uint32_t)std::strtoul(e, nullptr, 10);
     I.occ_force = I.occ_blocks == 0;
@@ -5784,7 +5723,6 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
     HIPCHK(hipStreamCreateWithPriority(&I.sstream, hipStreamNonBlocking, least));
-    if (const char* e = std::getenv("KSG_STATIC_SIDE")) I.static_side = std::strtol(e, nullptr, 10) != 0;
     if (const char* e = std::getenv("KSG_STATIC_DEC")) I.static_dec = (int)std::strtol(e, nullptr, 10);
     if (const char* e = std::getenv("KSG_STATIC_RUN_MB")) I.static_run_mb = (uint32_t)std::strtoul(e, nullptr, 10);
     if (const char* e = std::getenv("KSG_STATIC_OVERLAP")) I.static_overlap = (int)std::strtol(e, nullptr, 10);
@@ -5849,7 +5787,6 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
 }
 
 static uint32_t eval_tiles(uint32_t N, uint32_t cus);
-static uint32_t tt_ring();
 bool Engine::upload(const NodeSoA& ns, const PodTableSoA& pt, uint32_t pod_cap, uint32_t term_cap, uint32_t req_cap,
                     uint32_t val_cap, std::string& err) {
   Impl& I = *p_;
@@ -5977,8 +5914,7 @@ bool Engine::upload(const NodeSoA& ns, const PodTableSoA& pt, uint32_t pod_cap, 
     if (!I.carrive.alloc(1, err) || !I.cpi.alloc((size_t)KCP_I * I.cnblk, err) ||
         !I.cpst.alloc(I.cnblk, err) ||
         !I.cpm.alloc((size_t)2 * KCP_X * I.cnblk, err) || !I.cpm2.alloc((size_t)2 * I.cnblk, err) ||
-        !I.cpr.alloc((size_t)KSG_MAX_TSC * I.cnblk, err) || !I.cpk.alloc(I.cnblk, err) ||
-        !I.ccand.alloc((size_t)kChain * I.cnblk, err))
+        !I.cpr.alloc((size_t)KSG_MAX_TSC * I.cnblk, err) || !I.cpk.alloc(I.cnblk, err))
       return false;
     HIPCHK(hipMemsetAsync(I.carrive.p, 0, sizeof(uint32_t), s));
   }
@@ -6034,7 +5970,7 @@ bool Engine::upload(const NodeSoA& ns, const PodTableSoA& pt, uint32_t pod_cap, 
   if (I.batch_ok && I.R <= 4) {
     uint32_t T = eval_tiles(I.N, I.n_cus);
     size_t Nn = std::max<uint32_t>(I.N, 1);
-    if (!I.tile_top.alloc((size_t)tt_ring() * KSG_BATCH * T * KSG_TOPK, err) || !I.tfeas.alloc((size_t)tt_ring() * KSG_BATCH * T * 3, err) ||
+    if (!I.tile_top.alloc((size_t)2 * KSG_BATCH * T * KSG_TOPK, err) || !I.tfeas.alloc((size_t)2 * KSG_BATCH * T * 3, err) ||
         !I.arrive.alloc(2 * KSG_BATCH * 32, err) || !I.pend_n.alloc(2, err) || !I.wrec.alloc(2 * kRecBytes, err) ||
         !I.pend.alloc(2 * KSG_BATCH, err) || !I.bfilter.alloc(Nn * 2 * KSG_BATCH, err) ||
         !I.bscore.alloc(Nn * 2 * KSG_BATCH * KSG_MAX_PLUGINS, err) || !I.btotal.alloc(Nn * 2 * KSG_BATCH, err))
@@ -6052,21 +5988,8 @@ bool Engine::upload(const NodeSoA& ns, const PodTableSoA& pt, uint32_t pod_cap, 
 // replay block in one round; at most 16 (then several rounds).  (Tiles balanced
 // to fill every CU were measured slower: the replay block's memory latency
 // grows with the eval blocks around it.)
-// Windows' tile-list slots (KSG_TT_RING, default 2: window parity)
-static uint32_t tt_ring() {
-  static const uint32_t r = [] {
-    const char* e = std::getenv("KSG_TT_RING");
-    const uint32_t v = e ? (uint32_t)std::strtoul(e, nullptr, 10) : 2u;
-    return v < 2 ? 2u : (v > 64 ? 64u : v);
-  }();
-  return r;
-}
+// (The windows' tile lists have two slots, one per window parity.)
 static uint32_t eval_npt(uint32_t N, uint32_t cus) {
-  static const uint32_t forced = [] {  // KSG_WIN_NPT: nodes per thread of the window's eval tiles (A/B)
-    const char* e = std::getenv("KSG_WIN_NPT");
-    return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 0u;
-  }();
-  if (forced) return std::min<uint32_t>(forced, 16);
   uint32_t npt = 1;
   while (npt < 16 && (uint64_t)KSG_BATCH * ((N + KSG_TILE * npt - 1) / (KSG_TILE * npt)) + 1 > cus) ++npt;
   return npt;
@@ -6126,8 +6049,8 @@ static bool run_batches_split(Engine::Impl& I, const WinArgs& A0, uint32_t first
       a.stamps = nullptr;
       a.e0 = first + (uint32_t)E * KSG_BATCH;
       a.ne = std::min<uint32_t>(KSG_BATCH, first + count - a.e0);
-      a.tile_top = I.tile_top.p + (size_t)(E % tt_ring()) * tt_sz;
-      a.tile_feas = I.tfeas.p + (size_t)(E % tt_ring()) * tf_sz;
+      a.tile_top = I.tile_top.p + (size_t)(E & 1) * tt_sz;
+      a.tile_feas = I.tfeas.p + (size_t)(E & 1) * tf_sz;
       a.erec = I.xsend.p + (size_t)(E & 1) * kRecBytes;
       a.estamps = I.stamps_on ? I.stamps.p + (size_t)E * 32 : nullptr;
       a.pprev = I.pend.p + (size_t)(P & 1) * KSG_BATCH;
@@ -6215,12 +6138,10 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
   A.T = T;
   A.npt = npt;
   A.tile_len = tile_len;
-  // deferred tile merge (KSG_DEFER_MERGE=1, single shard): measured slower on
-  // cfg2 and cfg3 — merging 32 pods' tile lists costs the replay block ~9 us,
-  // more than the evaluation's own merge costs its chain
-  A.defer = 0;
+  // (a tile merge deferred to the replay block was measured slower on cfg2 and
+  // cfg3 and removed: merging 32 pods' tile lists cost the replay block ~9 us,
+  // more than the evaluation's own merge costs its chain)
   A.stash_npt = kStashNpt;
-  if (const char* e = std::getenv("KSG_DEFER_MERGE")) A.defer = (std::strtol(e, nullptr, 10) != 0 && I.xranks <= 1) ? 1u : 0u;
   const size_t tt_sz = (size_t)KSG_BATCH * T * KSG_TOPK, tf_sz = (size_t)KSG_BATCH * T * 3;
   A.tile_top = I.tile_top.p;
   A.tile_feas = I.tfeas.p;
@@ -6244,23 +6165,17 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
   }
   // static records: a ring of two chunks of whole windows (window j+1's eval and
   // window j's replay may sit in consecutive chunks); chunk c computed by k_static
-  // just before the launch that evaluates its first window
-  //
-  // Inline: chunk c is computed on the engine stream just before the launch
-  // that evaluates its first window (ring of 2 chunks).  Side stream (default):
-  // k_static runs on a low-priority stream two chunks ahead, on the CUs the
-  // window launches leave idle; ring of 3 chunks, two events per chunk:
-  // ready(c) before the launch evaluating chunk c's first window, and the slot
-  // of chunk c+2 free after the launch replaying chunk c-1's last window.
+  // on the engine stream just before the launch that evaluates its first window.
+  // (Chunks computed two ahead on the side stream, beside the window launches,
+  // were measured no faster — the windows slow down beside them — and removed.)
   const bool stat = I.batch_static;
-  const bool side = stat && I.sstream && I.static_side;
   // the persistent window loop over static records: every record of the run
   // computed before the launch (one chunk; the loop has no ring to roll), when
   // they fit KSG_STATIC_RUN_MB (default 16 GiB of the 288 GB)
   const bool persist_ok = !sharded && I.win_run_on && nwin > 0 && 1 + (uint64_t)KSG_BATCH * T <= I.n_cus;
   const uint32_t count32 = (count + KSG_BATCH - 1) / KSG_BATCH * KSG_BATCH;
   const uint64_t run_bytes = (uint64_t)count32 * std::max<uint32_t>(I.N, 1) * sizeof(StaticRec);
-  bool stat_run = stat && !side && persist_ok && I.static_run_mb > 0 && !I.stat_chunk_cap &&
+  bool stat_run = stat && persist_ok && I.static_run_mb > 0 && !I.stat_chunk_cap &&
                   run_bytes <= ((uint64_t)I.static_run_mb << 20);
   if (stat_run && run_bytes > I.stat.n * sizeof(StaticRec)) {
     // (a run-sized buffer only while it leaves most of the device free: another
@@ -6271,7 +6186,7 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
       stat_run = false;
     }
   }
-  uint32_t chunk = 0, nchunks = 0, nslots = 2;
+  uint32_t chunk = 0, nslots = 2;
   const bool gstat = stat && I.gstat && sharded;  // node-sharded: records over every node
   const DevCluster CS = gstat ? I.cluster_static() : C;
   const uint32_t SN = gstat ? I.G : I.N;
@@ -6281,13 +6196,12 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
   if (stat) {
     const size_t Nn = std::max<uint32_t>(SN, 1);
     auto size_ring = [&]() {
-      nslots = stat_run ? 1 : side ? 3 : 2;
-      const size_t budget = side ? ((size_t)32 << 20) : ((size_t)64 << 20);
+      nslots = stat_run ? 1 : 2;
+      const size_t budget = (size_t)64 << 20;
       chunk = (uint32_t)std::max<size_t>(KSG_BATCH, (budget / (Nn * sizeof(StaticRec))) / KSG_BATCH * KSG_BATCH);
       chunk = std::min<uint32_t>(chunk, count32);
       if (I.stat_chunk_cap) chunk = std::min<uint32_t>(chunk, I.stat_chunk_cap);  // tests: force ring roll-over
       if (stat_run) chunk = count32;
-      nchunks = (count + chunk - 1) / chunk;
     };
     size_ring();
     if (!I.stat.alloc((size_t)nslots * chunk * Nn, err)) {
@@ -6301,10 +6215,6 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
     A.stat = I.stat.p;
     A.stat_ring = nslots * chunk;
     A.mpred = I.mpred.p;
-    if (side && !I.sev_ready[0]) {
-      for (auto* e : {&I.sev_ready[0], &I.sev_ready[1], &I.sev_ready[2], &I.sev_free})
-        HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    }
   }
   // decoded pods (k_static_dec) when every pod of the chunk flattens and the
   // nodes' taints fit the id set (KSG_STATIC_DEC=0: the program-walking k_static)
@@ -6360,15 +6270,8 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
       I.stat_pods_sampled += cn;
       I.n_st++;
     }
-    if (side) HIPCHK(hipEventRecord(I.sev_ready[c % 3], st));
     return true;
   };
-  if (side) {  // the side stream starts after the engine stream's work so far (uploads, previous runs)
-    HIPCHK(hipEventRecord(I.sev_free, s));
-    HIPCHK(hipStreamWaitEvent(I.sstream, I.sev_free, 0));
-    for (uint32_t c = 0; c < std::min<uint32_t>(2, nchunks); ++c)
-      if (!issue_static(c, I.sstream)) return false;
-  }
   if (sharded && !stat) return run_batches_split(I, A, first, count, T, err);
   // the persistent window loop: one launch for every window (its blocks all
   // resident: one per CU); not co-resident -> the launch-per-window loop below
@@ -6392,7 +6295,7 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
     uint32_t side_blocks = 0;
     auto issue_side = [&]() -> bool {
       if (!issue_static(0, I.sstream, I.sready.p, side_grid, I.sready.p + sgroups)) return false;
-      HIPCHK(hipEventRecord(I.sev_ready[0], I.sstream));
+      HIPCHK(hipEventRecord(I.sev_ready, I.sstream));
       return true;
     };
     if (overlap) {
@@ -6401,8 +6304,8 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
       if (!I.sready.alloc(sgroups + 1, err) || !I.sd_pods.alloc((size_t)chunk * (sizeof(WcPod) / 8), err)) return false;
       HIPCHK(hipMemsetAsync(I.sready.p, 0, (sgroups + 1) * sizeof(uint32_t), s));
       HIPCHK(hipMemsetAsync(I.mpred.p, 0xFF, 2 * (size_t)count * sizeof(int64_t), s));
-      if (!I.sev_ready[0])
-        for (auto* e : {&I.sev_ready[0], &I.sev_ready[1], &I.sev_ready[2], &I.sev_free})
+      if (!I.sev_ready)
+        for (auto* e : {&I.sev_ready, &I.sev_free})
           HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
       HIPCHK(hipEventRecord(I.sev_free, s));
       HIPCHK(hipStreamWaitEvent(I.sstream, I.sev_free, 0));
@@ -6412,7 +6315,7 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
     }
     if (!I.wsync.alloc(1, err) || !I.rsync.alloc(1, err)) return false;
     if (!I.hverdict) {
-      HIPCHK(hipHostMalloc((void**)&I.hverdict, 64, hipHostMallocCoherent | hipHostMallocMapped));
+      HIPCHK(hipHostMalloc((void**)&I.hverdict, kVerdictBytes, hipHostMallocCoherent | hipHostMallocMapped));
       HIPCHK(hipMemsetAsync(I.rsync.p, 0, sizeof(RunSync), s));  // (the sticky abort word starts clear)
     }
     static bool wattr = false;
@@ -6483,7 +6386,7 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
     if (v == 1u) {
       I.win_runs++;
       if (overlap) {  // (the run's last kernel after the side stream's records)
-        HIPCHK(hipStreamWaitEvent(s, I.sev_ready[0], 0));
+        HIPCHK(hipStreamWaitEvent(s, I.sev_ready, 0));
         I.static_overlaps++;
       }
       const int64_t L = nwin - 1;
@@ -6497,17 +6400,15 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
     if (sampled) I.n_samples--;
     // (the side kernel's records and maxima are rewritten by the per-window loop's
     // k_static: it waits for the side kernel first)
-    if (overlap) HIPCHK(hipStreamWaitEvent(s, I.sev_ready[0], 0));
+    if (overlap) HIPCHK(hipStreamWaitEvent(s, I.sev_ready, 0));
   }
   for (int64_t j = -1; j < (int64_t)nwin; ++j) {
     const int64_t E = j + 1, W = j;
     A.ne = 0;
     A.nw = 0;
     A.stamps = A.estamps = nullptr;
-    A.tile_top = I.tile_top.p + (size_t)(E % tt_ring()) * tt_sz;
-    A.tile_feas = I.tfeas.p + (size_t)(E % tt_ring()) * tf_sz;
-    A.wtile_top = I.tile_top.p + (size_t)(W % tt_ring()) * tt_sz;
-    A.wtile_feas = I.tfeas.p + (size_t)(W % tt_ring()) * tf_sz;
+    A.tile_top = I.tile_top.p + (size_t)(E & 1) * tt_sz;
+    A.tile_feas = I.tfeas.p + (size_t)(E & 1) * tf_sz;
     if (E < (int64_t)nwin) {
       A.estamps = I.stamps_on ? I.stamps.p + (size_t)E * 32 : nullptr;
       A.e0 = first + (uint32_t)E * KSG_BATCH;
@@ -6527,10 +6428,7 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
     A.pprev_n = I.pend_n.p + (P & 1);
     const bool chunk_start = stat && A.ne && (A.e0 - first) % chunk == 0;
     const uint32_t cidx = chunk_start ? (A.e0 - first) / chunk : 0;
-    if (chunk_start) {
-      if (side) HIPCHK(hipStreamWaitEvent(s, I.sev_ready[cidx % 3], 0));
-      else if (!issue_static(cidx, s)) return false;
-    }
+    if (chunk_start && !issue_static(cidx, s)) return false;
     bool sampled = I.sample_every && A.ne && A.nw && I.n_samples * 2 + 2 <= I.sev.size();
     if (sampled) HIPCHK(hipEventRecord(I.sev[I.n_samples * 2], s));
     dim3 grid(1 + A.ne * T);
@@ -6545,11 +6443,6 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
     if (sampled) {
       HIPCHK(hipEventRecord(I.sev[I.n_samples * 2 + 1], s));
       I.n_samples++;
-    }
-    if (side && chunk_start && cidx + 2 < nchunks) {  // chunk cidx-1 fully replayed: its slot takes chunk cidx+2
-      HIPCHK(hipEventRecord(I.sev_free, s));
-      HIPCHK(hipStreamWaitEvent(I.sstream, I.sev_free, 0));
-      if (!issue_static(cidx + 2, I.sstream)) return false;
     }
     if (sharded && A.ne) {
       if (!xgather(I, kXchgBytes, err)) return false;
@@ -6670,8 +6563,7 @@ bool Engine::run_whatif(uint32_t first, uint32_t count, std::string& err) {
     // chunks whose records fit KSG_WHATIF_REC_MB (default 40 GiB of the 288 GB;
     // 0: pass 2 recomputes every pair).
     const uint32_t N = std::max<uint32_t>(I.N, 1);
-    size_t rec_mb = 40960;
-    if (const char* e = std::getenv("KSG_WHATIF_REC_MB")) rec_mb = (size_t)std::strtoull(e, nullptr, 10);
+    const size_t rec_mb = I.wi_rec_mb;
     int64_t wsum = 0;
     for (int i = 0; i < I.F.n; ++i)
       if (I.F.plugins[i] == KP_FIT || I.F.plugins[i] == KP_BA) wsum += I.F.weight[i] > 0 ? I.F.weight[i] : 0;
@@ -6684,7 +6576,7 @@ bool Engine::run_whatif(uint32_t first, uint32_t count, std::string& err) {
     bool use_cls = I.eval_mode == 1 && !I.any_eph_req && I.R <= 4 && I.static_fits && I.max_taints <= 4 &&
                    I.max_tid < 64 && !I.taint_dup && I.cols_small && rec_mb > 0 && wts_ok &&
                    100 * wsum < ((int64_t)1 << 24);
-    if (const char* e = std::getenv("KSG_WHATIF_CLASSES")) use_cls &= std::strtol(e, nullptr, 10) != 0;
+    use_cls &= I.wi_classes;
     for (uint32_t q = first; use_cls && q < first + count; ++q) {
       const uint32_t np = (I.prog_need[q] >> 8) & 0xFFu;
       use_cls = np <= 7 && ((I.max_taints + 1) << np) <= KSG_WC_CLS && (I.prog_need[q] & (1u << 16)) &&
@@ -6701,9 +6593,9 @@ bool Engine::run_whatif(uint32_t first, uint32_t count, std::string& err) {
     {
       int64_t wall = 0;
       for (int i = 0; i < I.F.n; ++i) wall += I.F.weight[i] > 0 ? I.F.weight[i] : 0;
-      A.small = 100 * wall < ((int64_t)1 << 31) && !std::getenv("KSG_WHATIF_WIDE") ? 1u : 0u;  // (WIDE: 64-bit path too)
+      A.small = 100 * wall < ((int64_t)1 << 31) && !I.wi_wide ? 1u : 0u;  // (WIDE: 64-bit path too)
     }
-    const bool narrow = A.bw_a + A.bw_t + A.bw_tot <= 30 && !std::getenv("KSG_WHATIF_WIDE");
+    const bool narrow = A.bw_a + A.bw_t + A.bw_tot <= 30 && !I.wi_wide;
     if (!narrow) { A.bw_a = 20; A.bw_t = 12; A.bw_tot = 30; }
     const size_t rbytes = narrow ? 4 : 8;
     uint32_t chunk = count;
@@ -6757,9 +6649,7 @@ bool Engine::run_whatif(uint32_t first, uint32_t count, std::string& err) {
           I.path_pods[3]++;
           WcPod* wp = reinterpret_cast<WcPod*>(I.wc_pods.p);
           hipLaunchKernelGGL(k_wc_decode, dim3((a.count + 63) / 64), dim3(64), 0, s, C, I.F, a, wp);
-          if (I.wc_npt == 1) hipLaunchKernelGGL(k_whatif_cls1<1>, gridc, dim3(256), 0, s, C, I.F, a, wp);
-          else if (I.wc_npt == 4) hipLaunchKernelGGL(k_whatif_cls1<4>, gridc, dim3(256), 0, s, C, I.F, a, wp);
-          else hipLaunchKernelGGL(k_whatif_cls1<2>, gridc, dim3(256), 0, s, C, I.F, a, wp);
+          hipLaunchKernelGGL(k_whatif_cls1<kWcNpt>, gridc, dim3(256), 0, s, C, I.F, a, wp);
           hipLaunchKernelGGL(k_whatif_cls2, dim3(a.count), dim3(KSG_WC_CLS), 0, s, I.F, a, tiles, I.xranks > 1 ? 1 : 0);
         } else if (pass == 2 && use_cls) {
           if (I.xranks > 1) hipLaunchKernelGGL(k_whatif_cls2, dim3(a.count), dim3(KSG_WC_CLS), 0, s, I.F, a, tiles, 2);
@@ -7430,14 +7320,14 @@ bool Engine::add_classes(const ClassUpload& u, std::string& err, const std::vect
     return p;
   };
   PcStage pst{I.nct, 0, I.ncreq, 0, I.ncval, 0, 0xFFFFFFFFu, {}, 0, {}, {}};  // (k_pc_build: the new classes' pool ranges)
-  if (I.pc_agg)  // slots with at most 256 domains: pc_dom counted per block
-    for (uint32_t sl = 0; sl < KSG_MAX_TOPO && sl < I.topo.topo_count.size() && sl < I.topo.nu_base.size(); ++sl) {
-      const uint32_t cnt = ((I.uniq >> sl) & 1u) ? I.N : I.topo.topo_count[sl];
-      if (I.topo.nu_base[sl] == 0xFFFFFFFFu || cnt == 0 || cnt > 256) continue;
-      pst.hbase[sl] = (uint16_t)pst.hsum;
-      pst.hcnt[sl] = (uint16_t)cnt;
-      pst.hsum += cnt;
-    }
+  // slots with at most 256 domains: pc_dom counted per block
+  for (uint32_t sl = 0; sl < KSG_MAX_TOPO && sl < I.topo.topo_count.size() && sl < I.topo.nu_base.size(); ++sl) {
+    const uint32_t cnt = ((I.uniq >> sl) & 1u) ? I.N : I.topo.topo_count[sl];
+    if (I.topo.nu_base[sl] == 0xFFFFFFFFu || cnt == 0 || cnt > 256) continue;
+    pst.hbase[sl] = (uint16_t)pst.hsum;
+    pst.hcnt[sl] = (uint16_t)cnt;
+    pst.hsum += cnt;
+  }
   if (npc) {  // definitions, rebased onto the device pools
     auto pc = held(u.pc);
     auto ct = held(u.ct);
@@ -7458,7 +7348,6 @@ bool Engine::add_classes(const ClassUpload& u, std::string& err, const std::vect
         ++pst.nk;
       }
     }
-    if (!I.pc_prefetch) pst.nk = 0xFFFFFFFFu;
     if (!up(I.pcls_d, pc0, *pc) || !up(I.cterm_d, I.nct, *ct) || !up(I.creq_d, I.ncreq, *rq) ||
         !up(I.cval_d, I.ncval, *cv) || !zero(I.pc_cnt, (size_t)pc0 * Nn, (size_t)npc * Nn) ||
         !zero(I.pc_dom, (size_t)pc0 * NUn, (size_t)npc * NUn) ||
@@ -7496,7 +7385,7 @@ bool Engine::add_classes(const ClassUpload& u, std::string& err, const std::vect
   // the cycle's program in the same upload (what k_place_program writes: program,
   // offset, PodLite, table row, fresh summary), so a pod that brings classes costs
   // one copy kernel, not two
-  if (prog && placed && fused && I.place_fused && !segs.empty() && prog->size() % 4 == 0) {
+  if (prog && placed && fused && !segs.empty() && prog->size() % 4 == 0) {
     const size_t q = I.prog_off.size();
     const size_t off = (I.prog_bytes + 255) & ~(size_t)255;
     if (!I.progs.grow(off + prog->size(), I.prog_bytes, s, err) || !I.prog_off_d.grow(q + 1, q, s, err) ||
@@ -7661,7 +7550,7 @@ bool Engine::view_arm_finish(std::string& err) {
   const size_t N = I.N, k = I.vp_k;
   hipLaunchKernelGGL(k_view, dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, I.stream, I.cluster(), I.F,
                      I.progs.p + I.prog_off[I.vp_q], I.sums.p + I.vp_q, I.kfilter.p + k * N,
-                     I.kscore.p + k * N * KSG_MAX_PLUGINS, I.vp_V, I.vblk.p, I.vp_hout, I.vdone.p);
+                     I.kscore.p + k * N * KSG_MAX_PLUGINS, I.vp_V, I.vblk.p, I.vp_hout);
   HIPCHK(hipGetLastError());
   return true;
 }
@@ -7698,8 +7587,6 @@ bool Engine::view_impl(uint32_t j, const ViewCfg& cfg, const ViewLayout& lay, ui
   V.off_norm = (uint32_t)lay.off_norm;
   V.off_rows = (uint32_t)lay.off_rows;
   V.n_norm = lay.n_norm;
-  V.narrow = I.view_narrow ? 1u : 0u;
-  V.slots_direct = I.view_slots_direct ? 1u : 0u;
   const size_t N = I.N, k = j - I.keep_first;
   hipStream_t s = I.stream;
   if (I.vblk_fresh) {  // a new block: generation 0 everywhere
@@ -7713,12 +7600,8 @@ bool Engine::view_impl(uint32_t j, const ViewCfg& cfg, const ViewLayout& lay, ui
   // the per-node arrays straight into the caller's pinned block when the device
   // can address it (one kernel, then only the slot table and summary are copied)
   uint8_t* hdev = N && !I.view_copy ? pinned_dev(host) : nullptr;
-  if (hdev && I.view_slots_direct)  // (k_view writes each slot as it claims it: the rest reads empty)
+  if (hdev)  // (k_view writes each slot as it claims it: the rest reads empty)
     std::memset(host, 0, (kViewSlots + 1) * sizeof(uint64_t));
-  if (hdev && !I.vdone.p) {
-    if (!I.vdone.alloc(1, err)) return false;
-    HIPCHK(hipMemsetAsync(I.vdone.p, 0, sizeof(uint32_t), s));
-  }
   if (arm) {  // (launched by the next run_queue's k_eval, or by view_arm_finish)
     if (!N || !hdev) { err = "view_arm: a direct view of a non-empty snapshot only"; return false; }
     I.vp_armed = true;
@@ -7732,7 +7615,7 @@ bool Engine::view_impl(uint32_t j, const ViewCfg& cfg, const ViewLayout& lay, ui
   if (N)
     hipLaunchKernelGGL(k_view, dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, s, I.cluster(), I.F, I.progs.p + I.prog_off[j],
                        I.sums.p + j, I.kfilter.p + k * N, I.kscore.p + k * N * KSG_MAX_PLUGINS, V, I.vblk.p,
-                       hdev ? hdev : I.vblk.p, I.vdone.p);
+                       hdev ? hdev : I.vblk.p);
   HIPCHK(hipGetLastError());
   if (!hdev) HIPCHK(hipMemcpyAsync(host, I.vblk.p, lay.bytes, hipMemcpyDeviceToHost, s));  // (direct: k_view wrote it all)
   if (!wait) return true;  // (queued behind the cycle's run: the caller's next sync completes it)
@@ -7941,12 +7824,6 @@ bool Engine::run_queue(uint32_t first, uint32_t count, bool commit, std::string&
   CA.stamps = I.cstamps_on ? I.cstamps.p : nullptr;
   CA.etot = nullptr;
   CA.xsend = nullptr;
-  CA.cand = I.ccand.p;
-  // one-launch cycles (k_eval_solo) for pods of normalising profiles whose outputs
-  // are not kept, unsharded, committing cycles only (a dry run reads the per-node
-  // filter codes, which k_eval_solo does not write); opt-in (KSG_SOLO=1): measured
-  // slower than the two-launch chain on cfg4 (63.6 vs 35.2 us/pod, r03)
-  const bool solo_ok = commit && !xchain && F.has_ext && I.solo == 1;
   if (I.cnblk > I.fold_blocks || xchain) {  // fold k_eval's partials once (k_fold, or the X2 merge) above this many blocks
     if (!I.cetot.alloc(1, err)) return false;
     CA.etot = I.cetot.p;
@@ -7999,7 +7876,7 @@ bool Engine::run_queue(uint32_t first, uint32_t count, bool commit, std::string&
   if (run_ok) {
     if (!I.rsync.alloc(1, err) || !I.rgran.alloc(4 * kRunSlot, err)) return false;
     if (!I.hverdict) {
-      HIPCHK(hipHostMalloc((void**)&I.hverdict, 64, hipHostMallocCoherent | hipHostMallocMapped));
+      HIPCHK(hipHostMalloc((void**)&I.hverdict, kVerdictBytes, hipHostMallocCoherent | hipHostMallocMapped));
       HIPCHK(hipMemsetAsync(I.rsync.p, 0, sizeof(RunSync), s));  // (the sticky abort word starts clear)
     }
   }
@@ -8076,20 +7953,6 @@ bool Engine::run_queue(uint32_t first, uint32_t count, bool commit, std::string&
       CA.q = j;
       CA.prog = prog;
       CA.xsend = xchain ? xs : nullptr;
-      if (solo_ok && !(I.prog_need[j] & 8) && !(I.keep_n && j >= I.keep_first && j < I.keep_first + I.keep_n)) {
-        const bool sampled = I.sample_every && (j % I.sample_every) == 0 && I.n_samples * 2 + 2 <= I.sev.size();
-        if (sampled) HIPCHK(hipEventRecord(I.sev[I.n_samples * 2], s));
-        if (rowm == 2) hipLaunchKernelGGL(k_eval_solo<2>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
-        else if (rowm == 1) hipLaunchKernelGGL(k_eval_solo<1>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
-        else hipLaunchKernelGGL(k_eval_solo<0>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
-        if (sampled) {
-          HIPCHK(hipEventRecord(I.sev[I.n_samples * 2 + 1], s));
-          I.n_samples++;
-        }
-        I.path_pods[2]++;
-        pending |= (CA.mode & 2) != 0;
-        continue;
-      }
       const bool sampled = I.sample_every && (j % I.sample_every) == 0 && I.n_samples * 2 + 2 <= I.sev.size();
       if (sampled) HIPCHK(hipEventRecord(I.sev[I.n_samples * 2], s));
       const bool occ = I.cnblk > (I.occ_blocks ? I.occ_blocks : 2 * I.n_cus) || I.occ_force;  // many blocks per CU
@@ -8131,7 +7994,7 @@ bool Engine::run_queue(uint32_t first, uint32_t count, bool commit, std::string&
           }
         }
         if (occ) hipLaunchKernelGGL(k_final_occ, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
-        else if ((pmask & ~kPmTab) == 0 && I.final_pm)  // (the plugin-set specialisation: kNPos)
+        else if ((pmask & ~kPmTab) == 0)  // (the plugin-set specialisation: kNPos)
           hipLaunchKernelGGL(k_final<kPmTab>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
         else hipLaunchKernelGGL(k_final<>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
       }
@@ -8244,8 +8107,8 @@ bool Engine::sync(std::string& err) {
   // the pinned verdict block: no second blocking round trip after the sync)
   const bool abort_async = I.run_used && I.hverdict;
   if (abort_async) {
-    __atomic_store_n(&I.hverdict[8], 0u, __ATOMIC_RELAXED);
-    HIPCHK(hipMemcpyAsync(&I.hverdict[8], I.rsync.p->abort, sizeof(uint32_t), hipMemcpyDeviceToHost, I.stream));
+    __atomic_store_n(&I.hverdict[kVerdictAbortWord], 0u, __ATOMIC_RELAXED);
+    HIPCHK(hipMemcpyAsync(&I.hverdict[kVerdictAbortWord], I.rsync.p->abort, sizeof(uint32_t), hipMemcpyDeviceToHost, I.stream));
   }
   if (!stream_sync(I, I.stream, err)) return false;
   I.hcalls.clear();  // every queued host exchange has run
@@ -8253,7 +8116,7 @@ bool Engine::sync(std::string& err) {
   if (I.run_used) {  // a persistent segment whose poll ran out left the launch early
     I.run_used = false;
     uint32_t ab = 0;
-    if (abort_async) ab = __atomic_load_n(&I.hverdict[8], __ATOMIC_ACQUIRE);
+    if (abort_async) ab = __atomic_load_n(&I.hverdict[kVerdictAbortWord], __ATOMIC_ACQUIRE);
     else HIPCHK(hipMemcpy(&ab, I.rsync.p->abort, sizeof(ab), hipMemcpyDeviceToHost));
     if (ab) {
       // the segment (and every later one of its call, which left at the handshake)

@@ -3352,8 +3352,6 @@ struct Cluster {
     }
     ~PreView() { drop(); }
   } pview;
-  bool classes_early = std::getenv("KSG_CLASSES_EARLY") && std::strtol(std::getenv("KSG_CLASSES_EARLY"), nullptr, 10) != 0;
-  bool view_prefetch = !(std::getenv("KSG_VIEW_PREFETCH") && std::strtol(std::getenv("KSG_VIEW_PREFETCH"), nullptr, 10) == 0);
   // arm: prepared before the cycle's run (Engine::view_arm), so that the run's k_eval
   // can write it itself (a profile without ScoreExtensions); the run's caller then
   // calls Engine::view_arm_finish
@@ -3420,15 +3418,7 @@ struct Cluster {
     } else {
       vector<uint8_t> blob;
       PodMeta m;
-      // classes_early: the pod's new classes registered and their tables built
-      // (one upload + k_pc_build on the engine stream) before its program is
-      // compiled, so the device builds them while the host compiles; the program
-      // then goes out on its own (k_place_program).  Otherwise the program rides
-      // in the class upload after the compile.
-      if (classes_early) {
-        register_classes(queue[q]);
-        if (!sync_classes()) return false;
-      }
+      // (the program rides in the upload of the classes it brings, after the compile)
       if (!compile(queue[q], (int32_t)(seq_base + q), blob, m)) return false;
       lap(2);
       bool placed = false;  // (with the classes it brought, in one upload)
@@ -3442,7 +3432,7 @@ struct Cluster {
     if (commit && !room_for(q)) return false;
     // (the summary's copy waits for the run; sync then only checks the run's state)
     if (!eng->keep_outputs(q, 1, err)) return false;
-    if (!commit && view_prefetch && !prefetch_view(q, true)) return false;  // (armed: the run may write it)
+    if (!commit && !prefetch_view(q, true)) return false;  // (armed: the run may write it)
     if (!eng->run_queue(q, 1, commit, err) || !eng->view_arm_finish(err)) return false;
     lap(4);
     if (!commit && pview.block && pview.q == (int64_t)q) {  // (the prefetched view carries the summary)

@@ -152,16 +152,14 @@ def test_whatif_pass_records(monkeypatch, env):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("npt", ["1", "2", "4"])
-def test_whatif_class_path_edge_selectors(monkeypatch, npt):
+def test_whatif_class_path_edge_selectors():
     """The class path's decoded pods (k_wc_decode: one flat requirement list per
     pod, failed-term masks in pass 1) on the NodeAffinity edge family: matchFields
     In / NotIn (PreFilterResult bitmaps and name requirements), field-only and
     empty terms, DoesNotExist / NotIn, Gt / Lt on non-numeric values, tolerations
     of every form, plus keys and values no node has and an empty nodeSelectorTerms
-    list; every nodes-per-thread variant of pass 1."""
+    list."""
     from ksg import edge
-    monkeypatch.setenv("KSG_WC_NPT", npt)
     doc = edge.generate_edge("na", n_pods=2 * STEP - 4)
     for p in doc["queue"]:  # (ephemeral-storage requests keep a step off the class path)
         for c in p["spec"]["containers"]:

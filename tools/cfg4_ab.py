@@ -1,5 +1,5 @@
 """cfg4 A/B: us per pod of the table chain with an engine switch off and on
-(--var: KSG_RUN persistent segments by default, KSG_SOLO one-launch cycles), same
+(--var: KSG_RUN, the persistent segments, by default), same
 cluster, results checked equal (and against the oracle on the first pods).
 usage: python tools/cfg4_ab.py [--var KSG_RUN] [--nodes N] [--pods P] [--check C]"""
 import argparse
@@ -30,7 +30,7 @@ t = time.perf_counter()
 for _ in range({steps}):
     s.reset(); s.schedule()
 dt = (time.perf_counter() - t) / {steps}
-print(json.dumps({{"us_per_pod": dt * 1e6 / {pods}, "paths": s.path_counts(True) + s.run_counts(),
+print(json.dumps({{"us_per_pod": dt * 1e6 / {pods}, "paths": s.path_counts() + s.run_counts(),
                   "res": [(r.selected, r.feasible, r.status) for r in s.results()]}}))
 """
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
