@@ -47,7 +47,9 @@ extern "C" {
  * ksg_abi_version() >= the version they were written against.  3: ksg_cycle_view
  * holds the Filter outcome once per node (fail_pos / fail_code / fail_msg) and
  * 32-bit scores per position, built on the device.  4: its score rows are as
- * narrow as their values allow (score_bytes / normalized_bytes; ksg_view_score). */
+ * narrow as their values allow (score_bytes / normalized_bytes; ksg_view_score).
+ * Added within 4 (no existing entry point or struct changed): ksg_ranked_nodes,
+ * ksg_ranked_node, KSG_RANK_MAX. */
 #define KSG_ABI_VERSION 4
 
 #define KSG_OK 0
@@ -280,6 +282,30 @@ int ksg_prescore_status(ksg_ctx* ctx, uint32_t q, uint32_t pos, int32_t* code, c
  * ScoreExtensions), computed on the device by the NormalizeScore the selection
  * used; valid where the node passed every filter. */
 int ksg_normalized_scores(ksg_ctx* ctx, uint32_t q, uint32_t pos, int64_t* out, uint32_t n);
+/* Ranked candidates: the min(k, feasible) best feasible nodes of queue pod q's
+ * cycle, best first, selected on the device from the pod's kept outputs (the
+ * pod of a ksg_cycle with either commit value, or a ksg_keep_outputs range; the
+ * lifetime of ksg_normalized_scores).  The order is the engine's own selection
+ * order: descending selection key (weighted total, then the seeded tie-break
+ * hash, then the node index) with the seed and queue index the pod's selection
+ * used, so out[0] is (result.selected, result.total) of a scheduled pod and the
+ * order is total, ties included (upstream selectHost reports its highest-scored
+ * nodes beside the winner).  `total` is the sum over the scoring positions of
+ * normalized score x framework weight (ksg_plugin_weights' *weight).  *n_out
+ * receives the count: 0 for an unschedulable pod or a cycle that ended in
+ * KSG_ERROR; 1, the selected node with the result's total, for a pod with one
+ * feasible node (upstream runs no scoring then).  k outside [1, KSG_RANK_MAX],
+ * out or n_out NULL, q outside the queue: KSG_E_RANGE; outputs not kept for q:
+ * KSG_E_STATE (as ksg_normalized_scores); a sharded context: KSG_E_INVALID.
+ * Changes no scheduling state; two calls on one pod return the same bytes.
+ * Env KSG_RANK_TILE (read at ksg_create): nodes per block of the select, a power
+ * of two in [128, 2048] (tests reach the multi-level merge with few nodes). */
+#define KSG_RANK_MAX 64
+typedef struct ksg_ranked_node {
+  int32_t node;   /* global node index */
+  int32_t total;  /* its weighted score */
+} ksg_ranked_node;
+int ksg_ranked_nodes(ksg_ctx* ctx, uint32_t q, uint32_t k, ksg_ranked_node* out, uint32_t* n_out);
 /* PostFilter (wrappedplugin.go:550-577 -> store.go:442 AddPostFilterResult):
  * DefaultPreemption's dry run for an unschedulable pod q (PodEligibleToPreemptOthers,
  * nodesWherePreemptionMightHelp, SelectVictimsOnNode, pickOneNodeForPreemption of

@@ -5348,6 +5348,7 @@ struct DBuf {
 constexpr size_t kVerdictBytes = 64;
 constexpr size_t kVerdictAbortWord = 8;
 static_assert((kVerdictAbortWord + 1) * sizeof(uint32_t) <= kVerdictBytes, "the abort word lies inside the verdict block");
+constexpr uint32_t kRankTile = 2048;  // ranked candidates: most nodes (keys) one block of 256 threads selects from
 struct Engine::Impl {
   EngineConfig cfg;
   // node-shard exchange (sharded batch path)
@@ -5527,6 +5528,12 @@ struct Engine::Impl {
   bool occ_force = false;
   DBuf<uint64_t> cpr, cpk;
   uint32_t cnblk = 0;
+  // ranked candidates (ranked.hip): nodes per block of the select (KSG_RANK_TILE: a power of two in
+  // [128, kRankTile]; tests force the multi-level merge), the tiles' partial top lists (two levels,
+  // ping-pong; kept across calls, freed by release_scratch) and the pinned block the result crosses in
+  uint32_t rank_tile = kRankTile;
+  DBuf<uint64_t> rk_part;
+  uint8_t* rk_host = nullptr;
   DBuf<int32_t> knorm;    // normalized scores of one kept pod
   DBuf<uint8_t> vblk;     // device cycle view block (Engine::view)
   bool vblk_fresh = true;
@@ -5667,6 +5674,7 @@ Engine::~Engine() {
   if (p_->hverdict) (void)hipHostFree(p_->hverdict);
   if (p_->apstage) (void)hipHostFree(p_->apstage);
   if (p_->vstage) (void)hipHostFree(p_->vstage);
+  if (p_->rk_host) (void)hipHostFree(p_->rk_host);
   if (p_->apstage_ev) (void)hipEventDestroy(p_->apstage_ev);
   if (p_->ev0) (void)hipEventDestroy(p_->ev0);
   if (p_->ev1) (void)hipEventDestroy(p_->ev1);
@@ -5685,6 +5693,11 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
   Impl& I = *p_;
   I.cfg = cfg;
   if (const char* e = std::getenv("KSG_FOLD_BLOCKS")) I.fold_blocks = (uint32_t)std::strtoul(e, nullptr, 10);
+  if (const char* e = std::getenv("KSG_RANK_TILE")) {  // the largest power of two <= the value, within [128, kRankTile]
+    const unsigned long v = std::strtoul(e, nullptr, 10);
+    I.rank_tile = 128;
+    while (I.rank_tile < kRankTile && 2ul * I.rank_tile <= v) I.rank_tile *= 2;
+  }
   if (const char* e = std::getenv("KSG_RUN")) I.run_on = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_RUN_BT")) I.run_bt = std::strtol(e, nullptr, 10) == 512 ? 512 : 256;
   if (const char* e = std::getenv("KSG_RUN_MIN")) I.run_min = std::max<uint32_t>(1, (uint32_t)std::strtoul(e, nullptr, 10));
@@ -6694,11 +6707,14 @@ bool Engine::run_whatif(uint32_t first, uint32_t count, std::string& err) {
 
 void Engine::release_scratch() {
   Impl& I = *p_;
-  if (!I.wrec_pairs.p) return;
+  if (!I.wrec_pairs.p && !I.rk_part.p) return;
   (void)hipStreamSynchronize(I.stream);
-  (void)hipFree(I.wrec_pairs.p);
+  if (I.wrec_pairs.p) (void)hipFree(I.wrec_pairs.p);
   I.wrec_pairs.p = nullptr;
   I.wrec_pairs.n = 0;
+  if (I.rk_part.p) (void)hipFree(I.rk_part.p);  // (ranked candidates: sized for the snapshot that is leaving)
+  I.rk_part.p = nullptr;
+  I.rk_part.n = 0;
 }
 
 // All-gather `bytes` from every rank into I.xrecv (rank order), on the engine stream.
@@ -8426,3 +8442,5 @@ extern "C" int ksg_debug_lane_selftest(int32_t* bad) {
   (void)hipFree(db);
   return rc;
 }
+
+#include "ranked.hip"

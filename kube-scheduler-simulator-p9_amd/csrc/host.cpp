@@ -5577,3 +5577,23 @@ int ksg_node_nonzero(ksg_ctx* ctx, int64_t* nonzero, uint32_t n) {
 }
 
 }  // extern "C"
+
+// The context's side of a lookup whose entry point lives in the engine's
+// translation unit (ksg_ranked_nodes, csrc/ranked.hip), so that this file, which
+// also links against a stand-in for the engine (tests/fuzz), needs no new Engine
+// member: the lock, the guard, the argument / queue-range check (KSG_E_RANGE), the
+// refusal of sharded contexts (KSG_E_INVALID), then fn on the engine with q's
+// program index (queue pod q is program q).  fn returns KSG_OK or a KSG_E* code
+// with its message in err, which becomes the context's last error.
+namespace ksg {
+int kept_pod_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
+                  int (*fn)(Engine& eng, uint32_t prog, void* user, std::string& err), void* user) {
+  KSG_LOCK(ctx);
+  KSG_GUARD(ctx);
+  auto& c = ctx->c;
+  if (!args_ok || q >= c.queue.size() || q >= c.meta.size()) return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
+  if (c.shards > 1) return ctx->fail(std::string(what) + ": not offered on a sharded context", KSG_E_INVALID);
+  const int rc = fn(*c.eng, q, user, c.err);
+  return rc == KSG_OK ? KSG_OK : ctx->fail(c.err, rc);
+}
+}  // namespace ksg

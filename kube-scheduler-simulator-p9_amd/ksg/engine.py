@@ -24,6 +24,13 @@ class _PodResult(ctypes.Structure):
                 ("skip_filter", ctypes.c_uint32), ("skip_score", ctypes.c_uint32), ("total", ctypes.c_int32)]
 
 
+RANK_MAX = 64  # KSG_RANK_MAX
+
+
+class _RankedNode(ctypes.Structure):
+    _fields_ = [("node", ctypes.c_int32), ("total", ctypes.c_int32)]
+
+
 class _Opts(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("stream", ctypes.c_void_p), ("shard_rank", ctypes.c_uint32),
                 ("shard_count", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
@@ -170,6 +177,7 @@ def load_library():
     L.ksg_filter_status.argtypes = [vp, u32, u32, u32, ctypes.POINTER(i32), cp, sz, ctypes.POINTER(sz)]
     L.ksg_prescore_status.argtypes = [vp, u32, u32, ctypes.POINTER(i32), cp, sz, ctypes.POINTER(sz)]
     L.ksg_normalized_scores.argtypes = [vp, u32, u32, ctypes.POINTER(i64), u32]
+    L.ksg_ranked_nodes.argtypes = [vp, u32, u32, ctypes.POINTER(_RankedNode), ctypes.POINTER(u32)]
     L.ksg_cycle_view_acquire.argtypes = [vp, u32, ctypes.POINTER(ctypes.POINTER(_CycleView))]
     L.ksg_cycle_view_release.argtypes = [ctypes.POINTER(_CycleView)]
     L.ksg_cycle_view_release.restype = None
@@ -486,6 +494,15 @@ class Scheduler:
         arr = (ctypes.c_int64 * n)()
         self._chk(self.L.ksg_normalized_scores(self.h, q, pos, arr, n), "ksg_normalized_scores")
         return list(arr)
+
+    def ranked_nodes(self, q, k=3):
+        """ksg_ranked_nodes: the min(k, feasible) best feasible nodes of kept pod q's cycle as
+        (global node index, weighted total) pairs, best first, in the engine's own selection
+        order (ties broken as the selection breaks them); 1 <= k <= RANK_MAX."""
+        arr = (_RankedNode * RANK_MAX)()
+        n = ctypes.c_uint32()
+        self._chk(self.L.ksg_ranked_nodes(self.h, q, k, arr, ctypes.byref(n)), "ksg_ranked_nodes")
+        return [(arr[i].node, arr[i].total) for i in range(n.value)]
 
     def node_nonzero(self):
         """NonZeroRequested (cpu milli, memory bytes) rows of every local node."""
