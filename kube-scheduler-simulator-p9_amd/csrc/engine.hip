@@ -415,15 +415,19 @@ __device__ __forceinline__ int32_t wave_max(int32_t v) { return __ockl_wfred_max
 __device__ __forceinline__ int32_t wave_sum(int32_t v) { return __ockl_wfred_add_i32(v); }
 __device__ __noinline__ int64_t div_i64_slow(int64_t x, int64_t a) { return x / a; }
 // floor(x / a) for 0 <= x, a > 0 — exact.  32-bit operands use the hardware
-// 32-bit divide; otherwise an estimate from one v_rcp_f64 (relative error
-// ~2^-50, so |estimate - quotient| < 1 for x < 2^52 with small quotients) is
-// corrected with exact 64-bit products.  Only BalancedAllocation's fractions
-// need an IEEE-rounded f64 division; integer quotients never do.
+// 32-bit divide; otherwise an estimate from one v_rcp_f64 is corrected with
+// exact 64-bit products.  v_rcp_f64 is an approximation (relative error near
+// 2^-28: div_small(2^32, 3) came out 4 low before the quotient gate below), so
+// |estimate - quotient| < 1 only for modest quotients: an estimate of 2^20 or
+// more, like x >= 2^52, takes the 64-bit divide.  The callers' quotients are
+// <= 100 x a plugin weight.  Only BalancedAllocation's fractions need an
+// IEEE-rounded f64 division; integer quotients never do.
 __device__ __forceinline__ int64_t div_small(int64_t x, int64_t a) {
   if ((uint64_t)x <= 0xFFFFFFFFull && (uint64_t)a <= 0xFFFFFFFFull) return (int64_t)((uint32_t)x / (uint32_t)a);
   if (x >= ((int64_t)1 << 52)) return div_i64_slow(x, a);
   int64_t q = (int64_t)((double)x * __builtin_amdgcn_rcp((double)a));
   if (q < 0) q = 0;
+  if (__builtin_expect(q >= ((int64_t)1 << 20), 0)) return div_i64_slow(x, a);
   if (q * a > x) q--;
   else if ((q + 1) * a <= x) q++;
   return q;
@@ -436,6 +440,29 @@ __device__ __forceinline__ uint32_t udiv_small(uint32_t x, uint32_t d) {
   return r < 0 ? q - 1 : ((uint32_t)r >= d ? q + 1 : q);
 }
 __device__ __forceinline__ bool lane0() { return (threadIdx.x & 63) == 0; }
+
+// BalancedAllocation's float64 steps (balanced_allocation.go balancedResourceScorer),
+// one Go operation each, shared by every restatement of the plugin below and by
+// k_selftest_arith: the fraction min(requested / allocatable, 1), the two-resource
+// deviation |f0 - f1| / 2, one squared deviation and the root of their mean for
+// more resources, and the score int64((1 - std) * 100).
+__device__ __forceinline__ double ba_frac(int64_t q, int64_t a) {
+  const double f = (double)q / (double)a;
+  return f > 1 ? 1 : f;
+}
+__device__ __forceinline__ double ba_sd2(double f0, double f1) { return fabs((f0 - f1) / 2); }
+__device__ __forceinline__ double ba_dev(double f, double mean) { return (f - mean) * (f - mean); }
+__device__ __forceinline__ double ba_sdn(double sum, int m) { return sqrt(sum / (double)m); }
+__device__ __forceinline__ int64_t ba_final(double sd) { return (int64_t)((1 - sd) * 100.0); }
+// a / ad from ad's correctly rounded reciprocal ra (the what-if class path: one
+// division per node instead of one per pair): q = a·ra, one exact remainder (FMA)
+// and q + r·ra — Markstein's correction, which returns the correctly rounded
+// quotient RN(a / ad), Go's float64 division, in 3 f64 operations instead of ~11
+// (integers a < 2^46, ad < 2^45 held in doubles: tests/test_markstein.py)
+__device__ __forceinline__ double wc_frac(double a, double ad, double ra) {
+  const double e = a * ra;
+  return __builtin_fma(__builtin_fma(-ad, e, a), ra, e);
+}
 
 // Go math.Log restated (oracle/ksg_oracle.cpp go_log); no contraction.
 __device__ double go_log(double x) {
@@ -615,15 +642,14 @@ __device__ int64_t ba_score(const DevCluster& C, const DevProfile& F, const Prog
     int64_t a, q;
     alloc_req(C, n, F.ba_res[i], V.h->ba_req[i], true, a, q);
     if (a == 0) continue;
-    double f = (double)q / (double)a;
-    if (f > 1) f = 1;
+    const double f = ba_frac(q, a);
     total = total + f;
     if (m == 0) f0 = f;
     else if (m == 1) f1 = f;
     m++;
   }
   if (m == 2) {
-    sd = fabs((f0 - f1) / 2);
+    sd = ba_sd2(f0, f1);
   } else if (m > 2) {
     double mean = total / (double)m;
     double sum = 0;
@@ -632,13 +658,11 @@ __device__ int64_t ba_score(const DevCluster& C, const DevProfile& F, const Prog
       int64_t a, q;
       alloc_req(C, n, F.ba_res[i], V.h->ba_req[i], true, a, q);
       if (a == 0) continue;
-      double f = (double)q / (double)a;
-      if (f > 1) f = 1;
-      sum = sum + (f - mean) * (f - mean);
+      sum = sum + ba_dev(ba_frac(q, a), mean);
     }
-    sd = sqrt(sum / (double)m);
+    sd = ba_sdn(sum, m);
   }
-  return (int64_t)((1 - sd) * 100.0);
+  return ba_final(sd);
 }
 
 __device__ __forceinline__ int64_t taint_score(const DevCluster& C, const ProgView& V, uint32_t n) {
@@ -1227,6 +1251,14 @@ __device__ __forceinline__ int64_t norm_div(int64_t x, int64_t mx) {
   return mx < ((int64_t)1 << 20) && x >= 0 && x <= 100 * mx ? (int64_t)udiv_small((uint32_t)x, (uint32_t)mx)
                                                               : div_small(x, mx);
 }
+// InterPodAffinity NormalizeScore (scoring.go): int64(100 * (s - min) / (max - min))
+// in float64, 0 when every node scored the same
+__device__ __forceinline__ int64_t ipa_norm(int64_t s, int64_t mn, int64_t mx) {
+  const int64_t diff = mx - mn;
+  double f = 0;
+  if (diff > 0) f = __dmul_rn(100.0, __ddiv_rn((double)(s - mn), (double)diff));
+  return (int64_t)f;
+}
 // NormalizeScore (wrappedplugin.go:400 -> the plugin's ScoreExtensions) of one
 // feasible node's raw score at a profile position, given the pod's normaliser
 // max / min over the feasible nodes: every path that selects (k_finalize, the
@@ -1255,10 +1287,7 @@ __device__ __forceinline__ int64_t normalize_pos(int plugin, const ksg_prog* h, 
     case KP_IPA: {
 #pragma clang fp contract(off)
       if (!(ipa_flags & 8u)) { use = false; return s; }  // PreScore Skip (empty topology score map)
-      const int64_t diff = mx - mn;
-      double f = 0;
-      if (diff > 0) f = __dmul_rn(100.0, __ddiv_rn((double)(s - mn), (double)diff));
-      return (int64_t)f;
+      return ipa_norm(s, mn, mx);
     }
     default: return s;  // no ScoreExtensions: the raw score
   }
@@ -2449,13 +2478,16 @@ __device__ __forceinline__ int64_t least_req(int64_t a, int64_t q) {  // leastRe
   return q > a ? 0 : div_small((a - q) * 100, a);
 }
 // leastRequestedScore for the compiled default arguments: floor((a-q)*100/a)
-// from one f64 reciprocal estimate (relative error ~2^-50, quotient <= 100, so
-// the truncated estimate is the quotient or one below it) and one exact
-// integer correction; branch-free unless (a-q)*100 >= 2^52.
+// from one f64 reciprocal estimate (relative error near 2^-28, quotient <= 100,
+// so the truncated estimate is the quotient or one beside it) and one exact
+// integer correction, branch-free.  Exact wherever x = (a-q)*100 fits int64
+// (0 <= q, a < 2^56): the conversions of x and a round by 2^-53, far inside the
+// estimate's own error, d <= 101 keeps d*a in int64, and the remainder is an
+// integer difference.  (A 2^52 gate to the 64-bit divide stood here; no operand
+// told the two apart, so it went.)
 __device__ __forceinline__ int64_t least_req_q(int64_t a, int64_t q) {
   if (q > a || a <= 0) return 0;
   int64_t x = (a - q) * 100;
-  if (__builtin_expect(x >= ((int64_t)1 << 52), 0)) return div_i64_slow(x, a);
   int64_t d = (int64_t)((double)x * __builtin_amdgcn_rcp((double)a));
   int64_t rem = x - d * a;
   return rem >= a ? d + 1 : (rem < 0 ? d - 1 : d);
@@ -2500,13 +2532,9 @@ __device__ __forceinline__ int64_t ba_score_row(const RowV& r, const DevProfile&
   if (MODE == 1) {
     bool ok0 = r.alloc[0] != 0, ok1 = r.alloc[1] != 0;
     if (ok0 && ok1) {
-      double f0 = (double)(r.req[0] + h->ba_req[0]) / (double)r.alloc[0];
-      double f1 = (double)(r.req[1] + h->ba_req[1]) / (double)r.alloc[1];
-      if (f0 > 1) f0 = 1;
-      if (f1 > 1) f1 = 1;
-      sd = fabs((f0 - f1) / 2);
+      sd = ba_sd2(ba_frac(r.req[0] + h->ba_req[0], r.alloc[0]), ba_frac(r.req[1] + h->ba_req[1], r.alloc[1]));
     }
-    return (int64_t)((1 - sd) * 100.0);
+    return ba_final(sd);
   }
   int m = 0;
   double total = 0, f0 = 0, f1 = 0;
@@ -2515,15 +2543,14 @@ __device__ __forceinline__ int64_t ba_score_row(const RowV& r, const DevProfile&
     int64_t a, q;
     alloc_req_row(r, F.ba_res_d[i], h->ba_req[i], true, a, q);
     if (a == 0) continue;
-    double f = (double)q / (double)a;
-    if (f > 1) f = 1;
+    const double f = ba_frac(q, a);
     total = total + f;
     if (m == 0) f0 = f;
     else if (m == 1) f1 = f;
     m++;
   }
   if (m == 2) {
-    sd = fabs((f0 - f1) / 2);
+    sd = ba_sd2(f0, f1);
   } else if (m > 2) {
     double mean = total / (double)m;
     double sum = 0;
@@ -2532,13 +2559,11 @@ __device__ __forceinline__ int64_t ba_score_row(const RowV& r, const DevProfile&
       int64_t a, q;
       alloc_req_row(r, F.ba_res_d[i], h->ba_req[i], true, a, q);
       if (a == 0) continue;
-      double f = (double)q / (double)a;
-      if (f > 1) f = 1;
-      sum = sum + (f - mean) * (f - mean);
+      sum = sum + ba_dev(ba_frac(q, a), mean);
     }
-    sd = sqrt(sum / (double)m);
+    sd = ba_sdn(sum, m);
   }
-  return (int64_t)((1 - sd) * 100.0);
+  return ba_final(sd);
 }
 
 // Evaluate one (pod, node row) for a Fit/BA profile: filter code, raw Fit and BA, total.
@@ -2670,6 +2695,19 @@ __device__ __forceinline__ uint64_t wave_merge_top(uint64_t v, uint64_t o_rev) {
 __device__ __forceinline__ uint64_t wave_reverse(uint64_t v) {
   return xor_lanes<32>(xor_lanes<16>(xor_lanes<8>(xor_lanes<4>(xor_lanes<2>(xor_lanes<1>(v))))));
 }
+// ksg_debug_arith's operations
+enum : int {
+  KSG_ARITH_DIV_SMALL = 0,    // x, a -> div_small
+  KSG_ARITH_LEAST_REQ_Q = 1,  // a, q -> least_req_q
+  KSG_ARITH_LEAST_REQ_D = 2,  // a, non-zero requested, pod request -> least_req_d
+  KSG_ARITH_UDIV_SMALL = 3,   // x, d -> udiv_small
+  KSG_ARITH_NORM_DIV = 4,     // x, mx -> norm_div
+  KSG_ARITH_WC_FRAC = 5,      // a, b -> bits of wc_frac(a, b, 1 / b)
+  KSG_ARITH_BA = 6,           // (q, a) x cols / 2 -> the BalancedAllocation score
+  KSG_ARITH_GO_LOG = 7,       // bits -> bits of go_log
+  KSG_ARITH_IPA_NORM = 8,     // s, mn, mx -> ipa_norm
+  KSG_ARITH_OPS = 9
+};
 // Self-test of the lane exchanges against ds_bpermute shuffles (diagnostic ABI).
 __global__ void k_selftest_lanes(const uint64_t* in, int32_t* bad) {
   const uint64_t v = in[threadIdx.x + blockIdx.x * 64];
@@ -2700,6 +2738,69 @@ __global__ void k_selftest_lanes(const uint64_t* in, int32_t* bad) {
     e += udiv_small(x, d) != x / d;
   }
   atomicAdd(bad, e);
+}
+
+// Self-test of the arithmetic fast paths (diagnostic ABI, ksg_debug_arith): the
+// engine's own __device__ functions applied element-wise to the caller's
+// operands, column c of element i at in[c * n + i]; doubles as bit patterns.
+__device__ __forceinline__ int64_t least_req_q(int64_t a, int64_t q);
+__device__ __forceinline__ int32_t least_req_d(double ad, double ra, double x);
+__device__ __forceinline__ int64_t d2bits(double v) { return (int64_t)__double_as_longlong(v); }
+__global__ __launch_bounds__(256) void k_selftest_arith(int op, const int64_t* __restrict__ in, uint32_t cols,
+                                                        int64_t* __restrict__ out, uint32_t n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t x = in[i], y = cols > 1 ? in[(size_t)n + i] : 0, z = cols > 2 ? in[2 * (size_t)n + i] : 0;
+  int64_t r = 0;
+  switch (op) {
+    case KSG_ARITH_DIV_SMALL: r = div_small(x, y); break;
+    case KSG_ARITH_LEAST_REQ_Q: r = least_req_q(x, y); break;
+    case KSG_ARITH_LEAST_REQ_D: {  // allocatable x, NonZeroRequested y, the pod's request z (k_whatif_cls1's WcNode)
+      const double ad = (double)x, ra = 1.0 / (ad != 0.0 ? ad : 1.0);
+      const double fx = (ad - (double)y) * 100.0, x0 = fx - (double)z * 100.0;
+      r = (ad != 0.0 && ad > 0.0 && x0 >= 0.0) ? least_req_d(ad, ra, x0) : 0;
+      break;
+    }
+    case KSG_ARITH_UDIV_SMALL: r = (int64_t)udiv_small((uint32_t)x, (uint32_t)y); break;
+    case KSG_ARITH_NORM_DIV: r = norm_div(x, y); break;
+    case KSG_ARITH_WC_FRAC: {  // x / y as the class path forms it
+      const double ad = (double)y, ra = 1.0 / (ad != 0.0 ? ad : 1.0);
+      r = d2bits(wc_frac((double)x, ad, ra));
+      break;
+    }
+    case KSG_ARITH_BA: {  // cols / 2 (requested, allocatable) pairs, as ba_score / ba_score_row walk them
+      const int k = (int)(cols / 2);
+      int m = 0;
+      double total = 0, f0 = 0, f1 = 0, sd = 0.0;
+      for (int c = 0; c < k; ++c) {
+        const int64_t q = in[(size_t)(2 * c) * n + i], a = in[(size_t)(2 * c + 1) * n + i];
+        if (a == 0) continue;
+        const double f = ba_frac(q, a);
+        total = total + f;
+        if (m == 0) f0 = f;
+        else if (m == 1) f1 = f;
+        m++;
+      }
+      if (m == 2) {
+        sd = ba_sd2(f0, f1);
+      } else if (m > 2) {
+        const double mean = total / (double)m;
+        double sum = 0;
+        for (int c = 0; c < k; ++c) {
+          const int64_t q = in[(size_t)(2 * c) * n + i], a = in[(size_t)(2 * c + 1) * n + i];
+          if (a == 0) continue;
+          sum = sum + ba_dev(ba_frac(q, a), mean);
+        }
+        sd = ba_sdn(sum, m);
+      }
+      r = ba_final(sd);
+      break;
+    }
+    case KSG_ARITH_GO_LOG: r = d2bits(go_log(__longlong_as_double(x))); break;
+    case KSG_ARITH_IPA_NORM: r = ipa_norm(x, y, z); break;
+    default: break;
+  }
+  out[i] = r;
 }
 
 // Per-pair output rows of queue pod q: the kept window, or a scratch ring of
@@ -3610,17 +3711,12 @@ __global__ __launch_bounds__(256) void k_whatif_cls1(DevCluster C, DevProfile F,
         if (hb) {
           double sd = 0.0;
           if (ok0 && ok1) {
-            // a / ad from the node's correctly rounded reciprocal y: q = a·y, then
-            // one exact remainder (FMA) and q + r·y — Markstein's correction, which
-            // returns the correctly rounded quotient (RN(a / ad), Go's float64
-            // division) without a division per pair (3 f64 ops instead of ~11)
-            const double a0 = v.rd0 + bq0, a1 = v.rd1 + bq1;
-            const double e0 = a0 * v.ra0, e1 = a1 * v.ra1;
-            double f0 = __builtin_fma(__builtin_fma(-v.ad0, e0, a0), v.ra0, e0);
-            double f1 = __builtin_fma(__builtin_fma(-v.ad1, e1, a1), v.ra1, e1);
+            // (requested + the pod's) / allocatable from the node's reciprocal (wc_frac)
+            double f0 = wc_frac(v.rd0 + bq0, v.ad0, v.ra0);
+            double f1 = wc_frac(v.rd1 + bq1, v.ad1, v.ra1);
             f0 = __builtin_fmin(f0, 1.0);  // (never NaN: the same as f > 1 ? 1 : f)
             f1 = __builtin_fmin(f1, 1.0);
-            sd = fabs((f0 - f1) / 2);
+            sd = ba_sd2(f0, f1);
           }
           // (a value outside int32 saturates: still < 0 or > 100, i.e. bad)
           const int32_t sc = __double2int_rz((1 - sd) * 100.0);
@@ -8440,6 +8536,25 @@ extern "C" int ksg_debug_lane_selftest(int32_t* bad) {
   }
   (void)hipFree(d);
   (void)hipFree(db);
+  return rc;
+}
+
+// Diagnostic: the arithmetic fast paths on caller-supplied operands
+// (tests/test_arith_gpu.py); in: cols columns of n operands, out: n results.
+extern "C" int ksg_debug_arith(int op, const int64_t* in, uint32_t cols, int64_t* out, uint32_t n) {
+  if (!in || !out || n == 0 || cols == 0 || cols > 8 || op < 0 || op >= ksg::KSG_ARITH_OPS) return -1;
+  int64_t *di = nullptr, *dout = nullptr;
+  const size_t ib = (size_t)cols * n * 8, ob = (size_t)n * 8;
+  if (hipMalloc((void**)&di, ib) != hipSuccess) return -2;
+  if (hipMalloc((void**)&dout, ob) != hipSuccess) { (void)hipFree(di); return -2; }
+  int rc = 0;
+  if (hipMemcpy(di, in, ib, hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+  if (!rc) {
+    hipLaunchKernelGGL(ksg::k_selftest_arith, dim3((n + 255) / 256), dim3(256), 0, 0, op, di, cols, dout, n);
+    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = -2;
+  }
+  (void)hipFree(di);
+  (void)hipFree(dout);
   return rc;
 }
 

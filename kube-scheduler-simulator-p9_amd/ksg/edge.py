@@ -674,3 +674,266 @@ def generate_edge(variant: str, **sizes) -> dict:
 
 def dumps(doc) -> str:
     return json.dumps(doc, separators=(",", ":"), sort_keys=False)
+
+
+# --------------------------------------------------------------------------- magnitude family
+# Clusters sized at the gates of the engine's arithmetic fast paths rather than
+# like real ones (DESIGN.md "Arithmetic gates"): quantities are plain integers.
+# Kept out of EDGE_VARIANTS, so that the edge seeds and parametrisations stay put.
+MAGNITUDE_KINDS = ("div32", "div52", "zero_over", "wc_gate", "norm20")
+WC_GATE_VIOLATIONS = (None, "node_alloc", "pod_req", "node_req")
+A52 = 100 * ((1 << 52) // 10000)  # the largest multiple of 100 whose 100-fold stays below 2^52
+MAG_PROFILES = ("default", "least4", "most", "rtc", "static", "pts")
+
+
+def magnitude_seed(kind: str) -> int:
+    return 20250131 * 100 + 80 + MAGNITUDE_KINDS.index(kind)
+
+
+def magnitude_profile(name: str, seed: int) -> dict:
+    """The profiles the family runs under: the default Fit + BalancedAllocation
+    arguments, LeastAllocated cpu:1 memory:2 over four resources, MostAllocated,
+    RequestedToCapacityRatio (BalancedAllocation over four resources in these
+    three), TaintToleration + NodeAffinity in front, PodTopologySpread."""
+    fit, ba = ("NodeResourcesFit", 1), ("NodeResourcesBalancedAllocation", 1)
+    if name == "static":
+        return make_profile([("TaintToleration", 3), ("NodeAffinity", 2), fit, ba], seed)
+    if name == "pts":
+        return make_profile([fit, ("PodTopologySpread", 2), ba], seed)
+    prof = make_profile([fit, ba], seed)
+    if name == "default":
+        return prof
+    pc = prof["pluginConfig"]
+    four = [{"name": "cpu", "weight": 1}, {"name": "memory", "weight": 2}, {"name": EPH, "weight": 1},
+            {"name": GPU, "weight": 3}]
+    if name == "least4":
+        pc["NodeResourcesFit"] = {"scoringStrategy": {"type": "LeastAllocated", "resources": four}}
+    elif name == "most":
+        pc["NodeResourcesFit"] = {"scoringStrategy": {"type": "MostAllocated", "resources": four}}
+    elif name == "rtc":
+        pc["NodeResourcesFit"] = {"scoringStrategy": {"type": "RequestedToCapacityRatio", "resources": [
+            {"name": "cpu", "weight": 2}, {"name": "memory", "weight": 1}, {"name": GPU, "weight": 1}],
+            "requestedToCapacityRatio": {"shape": [{"utilization": 0, "score": 0}, {"utilization": 40, "score": 8},
+                                                   {"utilization": 100, "score": 3}]}}}
+    else:
+        raise ValueError(name)
+    pc["NodeResourcesBalancedAllocation"] = {"resources": [{"name": n["name"], "weight": 1} for n in four]}
+    return prof
+
+
+def _mreq(cpu=None, mem=None, eph=None, gpu=None):
+    r = {}
+    if cpu is not None:
+        r["cpu"] = f"{cpu}m"
+    if mem is not None:
+        r["memory"] = str(mem)
+    if eph is not None:
+        r[EPH] = str(eph)
+    if gpu is not None:
+        r[GPU] = str(gpu)
+    return {"requests": r} if r else {}
+
+
+def _mnode(r, i, cpu, mem, eph=None, gpu=None, pods=110):
+    """A node of the family, with the ``na`` / ``pts`` families' labels and taints
+    (used by the profiles that have those plugins, inert under the others)."""
+    labels = {"mag": "1", "grp": f"g{i % 4}"}
+    if r.pct() < 85:
+        labels[ZONE] = f"zone-{r.below(4)}"
+    if r.pct() < 70:
+        labels["disk"] = r.pick(["ssd", "hdd", "nvme"])
+    if r.pct() < 80:
+        labels["gen"] = r.pick([str(g) for g in range(1, 9)] + ["x9"])
+    taints = [dict(t) for t in NA_TAINTS if r.pct() < 12]
+    n = node_obj(f"node-{i:07d}", cpu, mem, pods=pods, labels=labels, taints=taints)
+    al = n["status"]["allocatable"]
+    al["memory"] = str(mem)
+    if eph is not None:
+        al[EPH] = str(eph)
+    if gpu is not None:
+        al[GPU] = str(gpu)
+    n["status"]["capacity"] = dict(al)
+    return n
+
+
+def _mspec(r):
+    """Pod-side NodeAffinity / tolerations / spread constraints (inert without the plugins)."""
+    spec = {}
+    if r.pct() < 50:
+        spec["tolerations"] = [{"operator": "Exists"}] if r.pct() < 40 else [
+            {"key": t["key"], "operator": "Exists"} for t in NA_TAINTS if r.pct() < 50]
+    if r.pct() < 45:
+        spec["affinity"] = {"nodeAffinity": {"preferredDuringSchedulingIgnoredDuringExecution": [
+            {"weight": 1 + r.below(100), "preference": {"matchExpressions": [_na_expr(r, 0)]}}
+            for _ in range(1 + r.below(3))]}}
+    if r.pct() < 50:
+        spec["topologySpreadConstraints"] = [{
+            "maxSkew": 1 + r.below(3), "topologyKey": r.pick([ZONE, HOSTNAME]), "whenUnsatisfiable": "ScheduleAnyway",
+            "labelSelector": {"matchLabels": {"app": r.pick(APPS[:3])}}}]
+    return spec
+
+
+def _mpod(r, j, containers, spec=True):
+    return pod_obj(f"pod-{j:07d}", containers, labels={"app": r.pick(APPS[:3])}, ns=r.pick(NAMESPACES),
+                   **(_mspec(r) if spec else {}))
+
+
+def _mfill(e, node, **rq):
+    return pod_obj(f"ex-{e:07d}", [_mreq(**rq)], labels={"app": APPS[e % 3]}, node=node["metadata"]["name"])
+
+
+def _gen_div32(r, n_nodes, n_pods):
+    mems = [42949672, 42949673, (1 << 32) - 1, 1 << 32, (1 << 32) + 1]
+    cpus = [1, 999, 4294967295, 4294967296, 4294967295, 4294967296]
+    ephs = [1 << 50, (1 << 53) + 100, 4294967296, 42949673]
+    nodes, bound = [], []
+    for i in range(n_nodes):
+        nodes.append(_mnode(r, i, cpus[i % 6], mems[(i // 2) % 5], eph=ephs[i % 4], gpu=[4, 4294967296][i % 2]))
+        if i % 3 != 2:
+            bound.append(_mfill(i, nodes[i], cpu=[1, 250][cpus[i % 6] > 999], mem=1 + r.below(1 << 20),
+                                eph=1 + r.below(1 << 20)))
+    queue = []
+    for j in range(n_pods):
+        cpu = 1 if r.pct() < 12 else 100 * (1 + r.below(9)) + r.below(3)
+        extra = dict(eph=1 + r.below(1 << 30)) if r.pct() < 40 else {}
+        if r.pct() < 30:
+            extra["gpu"] = 1 + r.below(2)
+        queue.append(_mpod(r, j, [_mreq(cpu=cpu, mem=(1 + r.below(6)) * Mi + r.below(3), **extra)]))
+    return nodes, bound, queue
+
+
+def _gen_div52(r, n_nodes, n_pods):
+    mems = [A52, A52 + 100, 1 << 46, 1 << 50, (1 << 53) + 100, (1 << 56) + 100]
+    p0 = 1 << 40  # the memory request half of the queue shares: fillers put it on a quotient boundary
+    nodes, bound = [], []
+    for i in range(n_nodes):
+        a = mems[i % 6]
+        nodes.append(_mnode(r, i, 1000 * r.pick([8, 16, 64]), a, eph=mems[(i + 1) % 6], gpu=mems[(i + 2) % 6]))
+        k = 1 + r.below(60)
+        if i % 4 == 3:
+            fill = 1 + r.below(a // 4)
+        else:  # NonZeroRequested + p0 = k a / 100, or one above it (a is a multiple of 100 or 100 above one)
+            fill = k * (a // 100) - p0 + (i // 6) % 2
+            while fill <= 0:
+                k += 7
+                fill = k * (a // 100) - p0 + (i // 6) % 2
+        bound.append(_mfill(i, nodes[i], cpu=250, mem=fill, eph=1 + r.below(mems[(i + 1) % 6] // 3),
+                            gpu=1 + r.below(mems[(i + 2) % 6] // 3)))
+    queue = []
+    for j in range(n_pods):
+        mem = p0 if j % 2 == 0 else (1 << (30 + r.below(14))) + r.below(1 << 20)
+        extra = dict(eph=(1 << (20 + r.below(25))) + r.below(1000)) if r.pct() < 50 else {}
+        if r.pct() < 50:
+            extra["gpu"] = (1 << r.below(44)) + r.below(5)
+        queue.append(_mpod(r, j, [_mreq(cpu=100 * (1 + r.below(8)), mem=mem, **extra)]))
+    return nodes, bound, queue
+
+
+def _gen_zero_over(r, n_nodes, n_pods):
+    nodes, bound = [], []
+    for i in range(n_nodes):
+        k = i % 8
+        cpu = 0 if k in (0, 2) else 1000 * r.pick([4, 8])
+        mem = 0 if k in (1, 2) else Gi * r.pick([8, 16])
+        nodes.append(_mnode(r, i, cpu, mem, eph=Gi * 100 if k != 2 else 0, gpu=r.pick([0, 4])))
+        if k == 3:  # bound pods above allocatable: cpu, memory, both
+            bound.append(_mfill(i, nodes[i], cpu=cpu + 500, mem=Gi))
+        elif k == 4:
+            bound.append(_mfill(i, nodes[i], cpu=500, mem=mem + Gi))
+        elif k == 5:
+            bound += [_mfill(i, nodes[i], cpu=cpu, mem=mem), _mfill(n_nodes + i, nodes[i], cpu=1, mem=1)]
+        elif k >= 6:
+            bound.append(_mfill(i, nodes[i], cpu=250 * (1 + r.below(6)), mem=Gi * (1 + r.below(3))))
+    queue = []
+    for j in range(n_pods):
+        if j % 5 in (0, 3):
+            cs = [{}] if j % 2 else [{}, {}]  # no requests: Fit's filter returns early, scoring uses the defaults
+        else:
+            cs = [_mreq(cpu=100 * (1 + r.below(6)), mem=128 * Mi * (1 + r.below(6)))]
+        queue.append(_mpod(r, j, cs))
+    return nodes, bound, queue
+
+
+def _gen_wc_gate(r, n_nodes, n_pods, violate):
+    top, ptop = (1 << 45) - 1, (1 << 44) - 1
+    nodes, bound = [], []
+    for i in range(n_nodes):
+        cpu = top if i % 3 == 0 else (1 << (36 + r.below(9))) + r.below(1000)
+        mem = top if i % 4 == 0 else (1 << (38 + r.below(7))) + r.below(1 << 20)
+        n = _mnode(r, i, cpu, mem)
+        n["spec"].pop("taints", None)  # (taint ids and counts stay within the class path's limits)
+        nodes.append(n)
+        if i % 12 == 0:  # requested memory exactly at the limit (2^44 - 1 and 2^44), cpu one below it
+            bound += [_mfill(2 * i, n, cpu=ptop, mem=ptop), _mfill(2 * i + 1, n, cpu=ptop, mem=ptop + 1)]
+        elif i % 2:
+            bound.append(_mfill(2 * i, n, cpu=1 + r.below(cpu // 2), mem=1 + r.below(mem // 2)))
+    queue = []
+    for j in range(n_pods):
+        cpu = ptop if j % 7 == 0 else (1 << (20 + r.below(22))) + r.below(1000)
+        mem = ptop if j % 5 == 0 else (1 << (24 + r.below(18))) + r.below(1 << 20)
+        queue.append(_mpod(r, j, [_mreq(cpu=cpu, mem=mem)] if j % 11 else [{}], spec=False))
+    if violate == "node_alloc":
+        al = nodes[5]["status"]["allocatable"]
+        al["memory"] = str(1 << 45)
+        nodes[5]["status"]["capacity"] = dict(al)
+    elif violate == "pod_req":
+        queue[5]["spec"]["containers"][0]["resources"] = _mreq(cpu=1000, mem=1 << 44)
+    elif violate == "node_req":
+        bound.append(_mfill(9 * n_nodes, nodes[0], cpu=1, mem=1))  # (cpu stays in range: 2^45 - 1)
+    elif violate is not None:
+        raise ValueError(violate)
+    return nodes, bound, queue
+
+
+NORM20_TARGETS = ((1 << 20) - 1, 1 << 20, (1 << 20) + 1)
+
+
+def _gen_norm20(r, n_nodes, n_pods):
+    """Preferred NodeAffinity weights whose sum on the best nodes (grp g0, with
+    the mag label: every term matches) is exactly 2^20 - 1, 2^20, 2^20 + 1 from
+    pod to pod; the other groups score partial sums, nodes without "gen" less."""
+    nodes, bound = [], []
+    for i in range(n_nodes):
+        n = _mnode(r, i, 1000 * r.pick([16, 32, 64]), Gi * r.pick([64, 128, 256]))
+        if i % 4 == 0:
+            n["spec"].pop("taints", None)
+        nodes.append(n)
+        if i % 2:
+            bound.append(_mfill(i, n, cpu=250 * (1 + r.below(8)), mem=Gi * (1 + r.below(8))))
+    queue = []
+    for j in range(n_pods):
+        target = NORM20_TARGETS[j % 3]
+        wa, wc = 1 + r.below(target // 2), 1 + r.below(target // 4)
+        terms = [(wa, {"key": "mag", "operator": "Exists"}),
+                 (wc, {"key": "grp", "operator": "In", "values": ["g0", "g1"]}),
+                 (target - wa - wc, {"key": "grp", "operator": "In", "values": ["g0"]})]
+        spec = {"affinity": {"nodeAffinity": {"preferredDuringSchedulingIgnoredDuringExecution": [
+            {"weight": w, "preference": {"matchExpressions": [e]}} for w, e in terms]}},
+            "tolerations": [{"operator": "Exists"}] if j % 4 else []}
+        queue.append(pod_obj(f"pod-{j:07d}", [_mreq(cpu=100 * (1 + r.below(6)), mem=128 * Mi * (1 + r.below(6)))],
+                             labels={"app": r.pick(APPS[:3])}, **spec))
+    return nodes, bound, queue
+
+
+def gen_magnitude(kind, n_nodes=60, n_pods=96, seed=None, profile=None, violate=None):
+    """One document of the magnitude family.  profile: a name of MAG_PROFILES (default:
+    "static" for norm20, else "default"); violate: wc_gate's one-change siblings
+    (WC_GATE_VIOLATIONS: a node's memory at 2^45, a pod's memory request at 2^44, a
+    bound pod taking a node's requested memory to 2^45)."""
+    seed = magnitude_seed(kind) if seed is None else seed
+    r = Rng(seed)
+    if kind == "div32":
+        nodes, bound, queue = _gen_div32(r, n_nodes, n_pods)
+    elif kind == "div52":
+        nodes, bound, queue = _gen_div52(r, n_nodes, n_pods)
+    elif kind == "zero_over":
+        nodes, bound, queue = _gen_zero_over(r, n_nodes, n_pods)
+    elif kind == "wc_gate":
+        nodes, bound, queue = _gen_wc_gate(r, n_nodes, n_pods, violate)
+    elif kind == "norm20":
+        nodes, bound, queue = _gen_norm20(r, n_nodes, n_pods)
+    else:
+        raise ValueError(kind)
+    assert len(nodes) <= 192 and len(queue) <= 192
+    prof = magnitude_profile(profile or ("static" if kind == "norm20" else "default"), seed)
+    return {"profile": prof, "nodes": nodes, "pods": bound, "queue": queue}

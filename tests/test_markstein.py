@@ -4,7 +4,9 @@ once per node, q = RN(a*y), r = a - b*q (exact, one FMA) and RN(q + r*y) is the
 correctly rounded a/b (Markstein's correction) — Go's float64 division
 (balanced_allocation.go: requested / allocatable).  This checks the identity on
 the CPU (C, libm fma) over the domain the host admits to that kernel (cpu /
-memory below 2^45, requests below 2^46), at random and at the edges."""
+memory below 2^45, requests below 2^46), at random and at the edges.  The device
+code itself (wc_frac) runs on the same domain in tests/test_arith_gpu.py
+(test_wc_frac)."""
 import os
 import subprocess
 import tempfile
