@@ -2431,6 +2431,13 @@ struct WinArgs {
   uint32_t evd_need;
   const uint32_t* nxt_evd;  // persistent loop: the next window's record counter and its target (null: last)
   uint32_t nxt_need;
+  // persistent loop, two replay blocks (KSG_WIN_REPLAY2): replay(W) reads P_{W-1} and
+  // the prior records only once the other block published W-1 (*pub_wait >=
+  // pub_wait_need; null: window 0); everything else of its stage is requested before
+  uint32_t replay2;
+  const uint32_t* pub_wait;
+  uint32_t pub_wait_need;
+  uint64_t* rstamps;  // diagnostic (realtime): publish wait start, end; P_W published; or null
 };
 // the static record of (queue pod q, global node g); PER (the persistent loop,
 // whose records k_static_dec may still be writing beside it): an sc1 load
@@ -4613,13 +4620,25 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
   }
   STAMP(0);
   if (A.stamps && tid == 0) A.stamps[11] = __builtin_amdgcn_s_memrealtime();
-  const int np = ldv<PER>(A.pprev_n);
-  // (P_{W-1}'s nodes for wave 0's index, requested with the count, not after it)
-  const int32_t pn_all = wave == 0 && lane < KSG_BATCH ? ldv<PER>(&A.pprev[lane].node) : -1;
+  // (two replay blocks: P_{W-1} is the other block's; its loads follow the wait
+  // for that publish below, after everything else of the stage is requested)
+  const bool p_late = PER && A.pub_wait != nullptr;
+  int np = 0;
+  int32_t pn_all = -1;
+  uint64_t pv = 0;
+  constexpr int kRowW = (int)(sizeof(RowV) / 8), kPendW = (int)(sizeof(Pend) / 8);
+  auto p_loads = [&]() {
+    np = ldv<PER>(A.pprev_n);
+    // (P_{W-1}'s nodes for wave 0's index, requested with the count, not after it)
+    pn_all = wave == 0 && lane < KSG_BATCH ? ldv<PER>(&A.pprev[lane].node) : -1;
+  };
+  auto p_list_load = [&]() {
+    pv = tid < KSG_BATCH * kPendW ? ldv<PER>(reinterpret_cast<const uint64_t*>(A.pprev) + tid) : 0;
+  };
+  if (!p_late) p_loads();
   // ---- stage.  The small inputs (P_{W-1}, pods, counts) are loaded first and
   // stored at once; the candidate keys and rows stay in flight in registers
   // across the prior-node evaluations (vmcnt is in order) and land after them.
-  constexpr int kRowW = (int)(sizeof(RowV) / 8), kPendW = (int)(sizeof(Pend) / 8);
   const uint64_t* keys = rec_keys(A.wrec);
   const uint64_t* rows = reinterpret_cast<const uint64_t*>(rec_rows(A.wrec));
   const int nk = nb * KSG_CAND, nr = nb * KSG_STAGE * kRowW;
@@ -4645,7 +4664,7 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
   };
   if (prior_rec_in && !pr_late) prior_loads();
   {
-    const uint64_t pv = tid < KSG_BATCH * kPendW ? ldv<PER>(reinterpret_cast<const uint64_t*>(A.pprev) + tid) : 0;
+    if (!p_late) p_list_load();
     constexpr int kPodW = (int)(sizeof(PodLite) / 8);
     const uint64_t qv = tid < nb * kPodW ? reinterpret_cast<const uint64_t*>(A.plite + A.w0)[tid] : 0;
     const int32_t fv = tid < nb ? ldv<PER>(reinterpret_cast<const int32_t*>(A.wrec) + tid) : 0;
@@ -4670,37 +4689,61 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
       if constexpr (PER) rv[k] = i < nr ? ldv<true>(reinterpret_cast<const uint64_t*>(&PR[p].row[r]) + wd) : 0;
       else rv[k] = i < nr ? rows[(size_t)(p * KSG_CAND + r) * kRowW + wd] : 0;
     }
-    if (pr_late) {  // the keys and rows are in flight: wait for the window's prior steps, then their records
+    auto small_stores = [&]() {  // what P_{W-1} does not enter: pods, counts, cleared picks
+      if (tid < nb * kPodW) reinterpret_cast<uint64_t*>(L.pod)[tid] = qv;
+      if (tid < nb) L.feas[tid] = fv;
+      if (STAT && tid < nb) {
+        L.achT[tid] = aT;
+        L.achA[tid] = aA;
+        L.mt[tid] = m0;
+        L.ma[tid] = m1;
+        L.fbf[tid] = 0;
+      }
+      if (tid < 3 * KSG_BATCH) {
+        (&L.S[0][0])[tid] = -1;
+        (&L.O[0][0])[tid] = -1;
+      }
+      if (tid < KSG_HSLOTS) {
+#pragma unroll
+        for (int t = 0; t < 3; ++t) pick_clear(L.pick[t], tid);
+      }
+    };
+    if (p_late) small_stores();  // (ahead of the wait; the keys and rows stay in registers across it)
+    if (pr_late || p_late) {
+      // the keys and rows are in flight: wait for the other block's publish of W-1
+      // (two replay blocks), then for the window's prior steps; then P_{W-1} and
+      // the prior records
       if (tid == 0) {
-        bool ok = false;
-        for (uint32_t it = 0; it < A.spin; ++it) {
-          if (ld_sc1(A.evd_wait) >= A.evd_need) { ok = true; break; }
-          if ((it & 63u) == 63u && ld_sc1(A.abortw) != 0u) break;
-          __builtin_amdgcn_s_sleep(1);
+        bool ok = true;
+        if (p_late) {
+          ok = false;
+          if (A.rstamps) A.rstamps[0] = __builtin_amdgcn_s_memrealtime();
+          for (uint32_t it = 0; it < A.spin; ++it) {
+            if (ld_sc1(A.pub_wait) >= A.pub_wait_need) { ok = true; break; }
+            if ((it & 63u) == 63u && ld_sc1(A.abortw) != 0u) break;
+            __builtin_amdgcn_s_sleep(1);
+          }
+          if (A.rstamps) A.rstamps[1] = __builtin_amdgcn_s_memrealtime();
+        }
+        if (ok && pr_late) {
+          ok = false;
+          for (uint32_t it = 0; it < A.spin; ++it) {
+            if (ld_sc1(A.evd_wait) >= A.evd_need) { ok = true; break; }
+            if ((it & 63u) == 63u && ld_sc1(A.abortw) != 0u) break;
+            __builtin_amdgcn_s_sleep(1);
+          }
         }
         if (!ok) __hip_atomic_store(A.abortw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       lds_barrier();  // (no fence: the previous window's patch stores stay in flight)
-      prior_loads();
+      if (p_late) {
+        p_loads();
+        p_list_load();
+      }
+      if (pr_late) prior_loads();
     }
     if (tid < np * kPendW) reinterpret_cast<uint64_t*>(L.prior)[tid] = pv;
-    if (tid < nb * kPodW) reinterpret_cast<uint64_t*>(L.pod)[tid] = qv;
-    if (tid < nb) L.feas[tid] = fv;
-    if (STAT && tid < nb) {
-      L.achT[tid] = aT;
-      L.achA[tid] = aA;
-      L.mt[tid] = m0;
-      L.ma[tid] = m1;
-      L.fbf[tid] = 0;
-    }
-    if (tid < 3 * KSG_BATCH) {
-      (&L.S[0][0])[tid] = -1;
-      (&L.O[0][0])[tid] = -1;
-    }
-    if (tid < KSG_HSLOTS) {
-#pragma unroll
-      for (int t = 0; t < 3; ++t) pick_clear(L.pick[t], tid);
-    }
+    if (!p_late) small_stores();
     if (wave == 0) {  // index P_{W-1} (one wave: its LDS operations stay in order)
       const int32_t pnode = lane < np ? pn_all : -1;
       L.ptn[lane] = -1;
@@ -5022,6 +5065,39 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
     pre_fl = ld_sc1(A.flushed);
     pre_ev = A.nxt_evd ? ld_sc1(A.nxt_evd) : 0u;
   }
+  // (persistent loop) the eval blocks' outputs of this window are written before
+  // the replay patches or rewrites them
+  auto flushed_wait = [&]() {
+    if (tid == 0) {
+      bool ok = pre_fl >= A.flush_need;
+      for (uint32_t it = 0; !ok && it < A.spin; ++it) {
+        if (ld_sc1(A.flushed) >= A.flush_need) { ok = true; break; }
+        if ((it & 63u) == 63u && ld_sc1(A.abortw) != 0u) break;
+        __builtin_amdgcn_s_sleep(2);
+      }
+      if (!ok) __hip_atomic_store(A.abortw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    lds_barrier();  // (thread 0 acquired the count; the summaries' stores need no ack here)
+  };
+  auto exact_writes = [&]() {
+    unsigned long long fm = __ballot(lane < nb && L.fbf[lane & 31] != 0);
+    while (fm) {
+      const int b = __ffsll((long long)fm) - 1;
+      fm &= fm - 1;
+      win_exact_write<MODE, PER>(C, F, A, L, b, cur, R);
+    }
+  };
+  // Two replay blocks: the other block writes P_W into the node rows as soon as it
+  // is published, and win_exact_write reads the node rows as of this window's
+  // start, so a fallback pod's outputs (rare) are rewritten before the publish.
+  bool exact_early = false;
+  if constexpr (PER && STAT) {
+    if (A.replay2 && __ballot(lane < nb && L.fbf[lane & 31] != 0) != 0) {
+      exact_early = true;
+      flushed_wait();
+      exact_writes();
+    }
+  }
   // ---- flush: P_W first (the persistent loop publishes it at once: the eval
   // blocks of window W+2 wait for it), then summaries and per-pair patches
   const PickTab& T = L.pick[cur];
@@ -5053,7 +5129,13 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     STAMP(27);
     __syncthreads();
-    if (tid < 16) st_sc1(A.pub + tid * 32, A.pub_val);
+    // (two replay blocks publish in turn: a maximum, so that a replica never steps
+    // back whatever order the two blocks' stores to it are performed in)
+    if (tid < 16) {
+      if (A.replay2) __hip_atomic_fetch_max(A.pub + tid * 32, A.pub_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else st_sc1(A.pub + tid * 32, A.pub_val);
+    }
+    if (A.rstamps && tid == 0) A.rstamps[2] = __builtin_amdgcn_s_memrealtime();
   }
   STAMP(6);
   if (tid < nb) {
@@ -5068,17 +5150,8 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
     }
   }
   if constexpr (PER) {  // the eval blocks' outputs of this window are written before the patches
-    if (tid == 0) {
-      L.nxt_ok = A.nxt_evd && pre_ev >= A.nxt_need ? 1u : 0u;  // (read after the block's next barrier)
-      bool ok = pre_fl >= A.flush_need;
-      for (uint32_t it = 0; !ok && it < A.spin; ++it) {
-        if (ld_sc1(A.flushed) >= A.flush_need) { ok = true; break; }
-        if ((it & 63u) == 63u && ld_sc1(A.abortw) != 0u) break;
-        __builtin_amdgcn_s_sleep(2);
-      }
-      if (!ok) __hip_atomic_store(A.abortw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    lds_barrier();  // (thread 0 acquired the count; the summaries' stores need no ack here)
+    if (tid == 0) L.nxt_ok = A.nxt_evd && pre_ev >= A.nxt_need ? 1u : 0u;  // (read after the block's next barrier)
+    if (!exact_early) flushed_wait();
   }
   {
     const int32_t Sv = L.S[cur][lane & 31];
@@ -5104,14 +5177,7 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
       }
     }
   }
-  if (STAT) {
-    unsigned long long fm = __ballot(lane < nb && L.fbf[lane & 31] != 0);
-    while (fm) {
-      const int b = __ffsll((long long)fm) - 1;
-      fm &= fm - 1;
-      win_exact_write<MODE, PER>(C, F, A, L, b, cur, R);
-    }
-  }
+  if (STAT && !exact_early) exact_writes();
   STAMP(5);
   if (A.stamps && tid == 0) A.stamps[12] = __builtin_amdgcn_s_memrealtime();
 #undef STAMP
@@ -5202,8 +5268,34 @@ __global__ void k_rows_unpack(const RowV* recv, uint32_t ranks, uint32_t G, uint
 // output ring) are reused two windows later, after those waits.  A launch whose
 // blocks are not all resident leaves at the handshake (run_handshake) and the
 // host runs the launch-per-window loop instead.
+//
+// Two replay blocks (KSG_WIN_REPLAY2): blocks 0 and 1 replay the even and the odd
+// windows, the tile blocks start at block 2.  A replay carries nothing in LDS from
+// window to window (nxt_ok is per block and refers to the block's next window,
+// W+2), so the only new ordering is between replay(W-1) and replay(W):
+//   replay(W), W >= 1, waits for Z.replayed >= W (one replica, sc1) before it reads
+//             P_{W-1} (pend[(W-1)&1]) and, after that, polls Z.evd for the prior
+//             records.  What does not depend on P_{W-1} — the wait for the keys
+//             (Z.evk), the key and row loads (held in registers), pods, feasible
+//             counts, cleared tables — is done before that wait.
+//   The publish of W-1 follows vmcnt(0) and a barrier of its block, so by then
+//             P_{W-2} is written back to the node rows and P_{W-1} is complete in
+//             pend[(W-1)&1]; replay(W) reads nothing else replay(W-1) wrote.  The
+//             summaries and output patches of W-1 go to other pods' slots and may
+//             still be in flight; the kernel's end covers them.  One exception:
+//             win_exact_write reads the node rows as of the window's start, which
+//             replay(W) overwrites with P_{W-1} — with two blocks it runs before
+//             the publish (win_fixup).
+//   pend[W&1] held P_{W-2}; replay(W) overwrites it with P_W after Z.evd(W) (so
+//             the evaluation and prior steps of W, which read it, are done) and
+//             after the publish of W-1 (whose replay read P_{W-2} into LDS before).
+//   wrec[W&1] is read by replay(W) only before its publish, and rewritten by the
+//             evaluation of W+2 only after it: as with one block.
+//   Z.flushed gates the patches of W in the block that replayed W: unchanged.
+//   The replicas of Z.replayed are raised by an atomic maximum, since two blocks
+//             now write them.
 struct WinSync {
-  uint32_t replayed[16][32];  // windows replayed and published (block 0), one replica per 128-B line:
+  uint32_t replayed[16][32];  // windows replayed and published (the replay blocks), one replica per 128-B line:
                               // each eval block polls its own (blk % 16), not all one line
   uint32_t evd[2];        // per window parity: pods whose record is out (cumulative over the launch)
   uint32_t pad1[30];
@@ -5285,11 +5377,13 @@ __global__ __launch_bounds__(KSG_WIN_THREADS) void k_window_run(DevCluster C, De
   WinArgs A = A0;
   A.abortw = abortw;
   A.spin = RC.spin;
-  if (blockIdx.x == 0) {
+  // the replay blocks come first: block 0 alone, or (A0.replay2) blocks 0 and 1 in turn
+  const uint32_t nrep = A0.replay2 ? 2u : 1u;
+  if (blockIdx.x < nrep) {
     WinLDS& L = *reinterpret_cast<WinLDS*>(lds_raw);
     L.nxt_ok = 0;
     __syncthreads();
-    for (uint32_t W = 0; W < R.nwin; ++W) {
+    for (uint32_t W = blockIdx.x; W < R.nwin; W += nrep) {
       const bool ready = L.nxt_ok != 0;  // (the previous replay saw this window's records complete)
       A.ne = 0;
       A.w0 = R.first + W * KSG_BATCH;
@@ -5320,8 +5414,12 @@ __global__ __launch_bounds__(KSG_WIN_THREADS) void k_window_run(DevCluster C, De
       A.evd_need = need;
       A.pub = &Z->replayed[0][0];
       A.pub_val = W + 1;
-      if (W + 1 < R.nwin) {
-        const uint32_t w1 = W + 1, nw1 = min((uint32_t)KSG_BATCH, R.first + R.count - (R.first + w1 * KSG_BATCH));
+      // (two replay blocks: P_{W-1} and the node rows under it are the other block's)
+      A.pub_wait = nrep > 1 && W >= 1 ? &Z->replayed[blockIdx.x][0] : nullptr;
+      A.pub_wait_need = W;
+      A.rstamps = R.stamps ? R.stamps + (size_t)R.nwin * 36 + (size_t)W * 4 : nullptr;
+      if (W + nrep < R.nwin) {  // (this block's next window)
+        const uint32_t w1 = W + nrep, nw1 = min((uint32_t)KSG_BATCH, R.first + R.count - (R.first + w1 * KSG_BATCH));
         A.nxt_evd = split ? &Z->evk[w1 & 1] : &Z->evd[w1 & 1];
         A.nxt_need = (w1 >> 1) * KSG_BATCH + nw1;
       } else {
@@ -5333,8 +5431,8 @@ __global__ __launch_bounds__(KSG_WIN_THREADS) void k_window_run(DevCluster C, De
     return;
   }
   uint64_t* const L = reinterpret_cast<uint64_t*>(lds_raw);
-  if (A0.mblocks && blockIdx.x >= 1 + KSG_BATCH * R.T) {  // the merge block of pod b
-    const uint32_t b = blockIdx.x - 1 - KSG_BATCH * R.T;
+  if (A0.mblocks && blockIdx.x >= nrep + KSG_BATCH * R.T) {  // the merge block of pod b
+    const uint32_t b = blockIdx.x - nrep - KSG_BATCH * R.T;
     for (uint32_t E = 0; E < R.nwin; ++E) {
       A.nw = 0;
       A.e0 = R.first + E * KSG_BATCH;
@@ -5358,7 +5456,7 @@ __global__ __launch_bounds__(KSG_WIN_THREADS) void k_window_run(DevCluster C, De
     }
     return;
   }
-  const uint32_t blk = blockIdx.x - 1, b = blk / R.T;
+  const uint32_t blk = blockIdx.x - nrep, b = blk / R.T;
   for (uint32_t E = 0; E < R.nwin; ++E) {
     A.nw = 0;
     A.e0 = R.first + E * KSG_BATCH;
@@ -5606,6 +5704,9 @@ struct Engine::Impl {
   DBuf<WinSync> wsync;           // k_window_run's counters (zeroed per launch)
   int win_run_on = 1;            // persistent window loop (k_window_run): KSG_WIN_RUN=0 turns it off
   int win_mblocks = 0;           // ... with dedicated merge blocks (KSG_WIN_MB=1; the last tile block merges: measured faster)
+  int win_replay2 = 1;           // ... two replay blocks, even / odd windows (KSG_WIN_REPLAY2; measured faster with
+                                 // KSG_WIN_PFIX=1 on Fit / BalancedAllocation profiles, slower on static ones)
+  int win_replay2_stat = 0;      // ... the same for Taint / NodeAffinity profiles
   int view_copy = 0;             // cycle view: 1 = the per-node arrays by a copy (KSG_VIEW_COPY), 0 = written by k_view
   int view_fuse = 1;             // fused views (Engine::view_arm; KSG_VIEW_FUSE=0: k_view always)
   bool vp_armed = false, vp_fused = false, vp_last_fused = false;  // the armed view and its launch parameters
@@ -5617,7 +5718,8 @@ struct Engine::Impl {
   int run_overlap = 0;           // k_chain_run: pod k+1's class-table reads during pod k's hand-offs (KSG_RUN_OVERLAP=1; measured no faster)
   int run_defer = 1;             // k_chain_run: the owner's independent node-level assume deferred (KSG_RUN_DEFER=0: off)
   int win_split = 1;             // ... split hand-over: keys staged while the prior steps run (KSG_WIN_SPLIT=0: one counter)
-  int win_pfix = 0;              // ... the replay evaluates the prior step itself (KSG_WIN_PFIX=1; measured slower)
+  int win_pfix = -1;             // ... the replay evaluates the prior step itself (KSG_WIN_PFIX=1) or the merges do (0);
+                                 // unset: as measured — the replay on static profiles and with two replay blocks
   uint64_t win_runs = 0, win_fallbacks = 0;  // diagnostic: persistent window launches / not co-resident
   uint32_t fold_blocks = 256;  // table chain: k_fold above this many blocks (KSG_FOLD_BLOCKS; tests force it)
   uint32_t occ_blocks = 0;     // table chain: occupancy twins above this many blocks (0: 2 per CU; KSG_OCC_BLOCKS)
@@ -5802,6 +5904,7 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
   if (const char* e = std::getenv("KSG_WIN_RUN")) I.win_run_on = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_WIN_MB")) I.win_mblocks = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_WIN_PFIX")) I.win_pfix = (int)std::strtol(e, nullptr, 10);
+  if (const char* e = std::getenv("KSG_WIN_REPLAY2")) I.win_replay2 = I.win_replay2_stat = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_WIN_SPLIT")) I.win_split = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_RUN_OVERLAP")) I.run_overlap = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_RUN_DEFER")) I.run_defer = (int)std::strtol(e, nullptr, 10);
@@ -6386,8 +6489,11 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
   // resident: one per CU); not co-resident -> the launch-per-window loop below
   if (persist_ok && (!stat || stat_run)) {
     // dedicated merge blocks (one per pod) when they fit beside the tile blocks
-    const bool mb = I.win_mblocks && 1 + (uint64_t)KSG_BATCH * (T + 1) <= I.n_cus;
-    const uint32_t grid = 1 + KSG_BATCH * T + (mb ? KSG_BATCH : 0);
+    // (two replay blocks when the extra block fits as well)
+    const bool r2 = (stat ? I.win_replay2_stat : I.win_replay2) && 2 + (uint64_t)KSG_BATCH * T <= I.n_cus;
+    const uint32_t nrep = r2 ? 2u : 1u;
+    const bool mb = I.win_mblocks && nrep + (uint64_t)KSG_BATCH * (T + 1) <= I.n_cus;
+    const uint32_t grid = nrep + KSG_BATCH * T + (mb ? KSG_BATCH : 0);
     // the run's records: before the launch, or (KSG_STATIC_OVERLAP, default)
     // beside it — k_static_dec_run, one 1,024-thread block per CU the loop leaves
     // idle, launched on the side stream BEFORE the loop (its blocks then hold
@@ -6457,7 +6563,8 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
     WinArgs AP = A;
     AP.mblocks = mb ? 1u : 0u;
     AP.astride = 32;
-    AP.prior_fix = I.win_pfix ? 1u : 0u;
+    AP.prior_fix = (I.win_pfix >= 0 ? I.win_pfix != 0 : (stat || r2)) ? 1u : 0u;
+    AP.replay2 = r2 ? 1u : 0u;
     AP.split = I.win_split ? 1u : 0u;
     __atomic_store_n(I.hverdict, 0u, __ATOMIC_RELEASE);
     RunCtl RC{grid + I.run_need_extra, I.run_wait_us * 100u, 0, I.hverdict, I.run_spin};

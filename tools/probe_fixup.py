@@ -4,7 +4,9 @@ Per window W, 24 slots at [W*24]: fixup block (shader clock) 0 start, 1 staged,
 2 prior-node evaluations, 3 starting guess, 4 Jacobi converged, 5 flushed,
 7 Jacobi iterations; realtime (100 MHz): 8 ~first eval-block start of window W
 (evaluated one launch earlier), 9 last tile eval done, 10 last merge done,
-11 fixup start, 12 fixup end.
+11 fixup start, 12 fixup end.  After the windows' slots: 4 per window of the
+persistent loop's top, then 4 per window of its publishes (publish wait start and
+end with two replay blocks, P_W published).
 """
 import ctypes
 import os
@@ -77,6 +79,20 @@ if any(x[0] for x in lt):
     print("realtime (us): loop-top wait", med([(lt[j][2] - lt[j][0]) / 100 for j in range(2, nw)]),
           "(not ready only:", med([(lt[j][2] - lt[j][0]) / 100 for j in range(2, nw) if not lt[j][1]] or [0]), ")")
     print("realtime (us): after wait -> fixup start", med([(bs[j][11] - lt[j][2]) / 100 for j in range(2, nw)]))
+# per window, after the loop-top slots: publish wait start / end of a second replay block, P_W published (realtime)
+rp = [buf[nw * 36 + j * 4:nw * 36 + (j + 1) * 4] for j in range(nw)]
+if any(x[2] for x in rp):
+    print("realtime (us): publish -> publish", med([(rp[j][2] - rp[j - 1][2]) / 100 for j in range(2, nw)]))
+    print("realtime (us): publish of W -> fixup W end (summaries, patches)", med([(bs[j][12] - rp[j][2]) / 100 for j in range(1, nw)]))
+if any(x[1] for x in rp):  # two replay blocks (KSG_WIN_REPLAY2=1): the stage above includes the publish wait
+    w = [(rp[j][1] - rp[j][0]) / 100 for j in range(2, nw)]
+    print("realtime (us): publish wait of replay W median", med(w), "mean", round(sum(w) / len(w), 2), "max", max(w))
+    print("realtime (us): fixup W start -> publish wait start (pre-stage)", med([(rp[j][0] - bs[j][11]) / 100 for j in range(2, nw)]))
+    print("realtime (us): publish of W-1 -> seen by replay W", med([(rp[j][1] - rp[j - 1][2]) / 100 for j in range(2, nw)]))
+    print("realtime (us): publish of W-1 seen -> publish of W (stage rest + core)", med([(rp[j][2] - rp[j][1]) / 100 for j in range(2, nw)]))
+    ov = [max(0, min(bs[j - 1][12], rp[j][2]) - max(rp[j - 1][2], rp[j][1])) / 100 for j in range(2, nw)]
+    print("realtime (us): flush of W-1 overlapping the core of W median", med(ov), "mean", round(sum(ov) / len(ov), 2))
+    print("realtime (us): fixup W end -> fixup W+2 start (same block)", med([(bs[j][11] - bs[j - 2][12]) / 100 for j in range(3, nw)]))
 two = [x for x in bs[1:] if x[7] >= 2]
 if two:
     print("iteration 2 median", med([x[20] - x[19] for x in two]), "windows", len(two))
