@@ -2401,7 +2401,9 @@ struct WinArgs {
   // sharded: replica of every node's row, indexed by global node (kept in step by
   // every rank's identical replay); null on one shard
   RowV* xrows;
-  // persistent window loop (k_window_run): the eval blocks count their window's
+  // persistent window loop (k_window_run): a pod's merge hands its keys, shallow
+  // rows and counts over to the replay, which evaluates the window's pods on
+  // P_{W-1} itself (as k_window's does); the eval blocks count their window's
   // finished pod records (evd) and written outputs (flushed); the replay waits for
   // flush_need of them before it patches outputs; abortw / spin bound every wait
   uint32_t* evd;
@@ -2411,29 +2413,12 @@ struct WinArgs {
   uint32_t spin;
   uint32_t* pub;      // the replicated "windows replayed" flag (16 lines of 32 words) and the value
   uint32_t pub_val;   // replay(W) publishes once P_W is out: W + 1
-  const Pend* pcur;   // eval side: P_{E-1} and its count, published when *pubw >= pub_need
-  const int32_t* pcur_n;
-  const uint32_t* pubw;
-  uint32_t pub_need;
-  uint32_t mblocks;   // persistent loop: dedicated merge blocks (one per pod) merge the tile lists
   uint32_t astride;   // arrival counter stride (u32): 1, or 32 in the persistent loop (a line per pod)
-  // persistent loop: 1 = the replay evaluates its window's pods on P_{W-1} itself
-  // (the merges hand over keys and rows without waiting for P_{W-1}); 0 = the
-  // merges do it once P_{W-1} is published (PriorRec)
-  uint32_t prior_fix;
-  // persistent loop, split hand-over (KSG_WIN_SPLIT=1): a merge counts its keys and
-  // shallow rows out (evk) before its prior step, so the replay stages them while the
-  // prior steps run and waits for the records (evd_wait >= evd_need; null: not split)
-  // only before it reads the PriorRecs
-  uint32_t split;
-  uint32_t* evk;
-  const uint32_t* evd_wait;
-  uint32_t evd_need;
   const uint32_t* nxt_evd;  // persistent loop: the next window's record counter and its target (null: last)
   uint32_t nxt_need;
-  // persistent loop, two replay blocks (KSG_WIN_REPLAY2): replay(W) reads P_{W-1} and
-  // the prior records only once the other block published W-1 (*pub_wait >=
-  // pub_wait_need; null: window 0); everything else of its stage is requested before
+  // persistent loop, two replay blocks (KSG_WIN_REPLAY2): replay(W) reads P_{W-1}
+  // only once the other block published W-1 (*pub_wait >= pub_wait_need; null:
+  // window 0); everything else of its stage is requested before
   uint32_t replay2;
   const uint32_t* pub_wait;
   uint32_t pub_wait_need;
@@ -3886,35 +3871,25 @@ struct PatchV {
   int32_t total;
   uint32_t raw;   // static record's raw Taint / NodeAffinity scores
 };
-// Persistent window loop: what the pod's merging eval block adds to the window's
-// candidate record (in the rows area, which the replay then no longer reads): the
-// pod evaluated on P_{W-1}'s nodes once the previous replay publishes them — the
-// replay's "prior" step, off its critical path — and the rows of its shallow
-// candidate ranks.  Deeper ranks' rows come from the node rows: a candidate that
-// is no P_{W-1} node has the same row at the end of W-1 as at the end of W-2.
-struct PriorRec {
-  uint64_t pkey[KSG_BATCH];  // key on prior node e (0: infeasible)
-  PatchV patch[KSG_BATCH];
-  int32_t pdf[KSG_BATCH];    // feasible-count change vs the snapshot (byte 0); Taint / NodeAffinity profiles:
-                             // the static-max achievers' changes in bytes 1 / 2 (each an int8)
-  RowV row[KSG_STAGE];       // rows of candidate ranks < KSG_STAGE (window-start rows)
-  uint64_t pmask, pbest;     // candidates that are prior nodes; the best prior key
-  int32_t pbest_e, np;
+// Persistent window loop: the rows a pod's merge puts into the window's candidate
+// record (packed per pod at the start of the rows area): those of its shallow
+// candidate ranks only.  Deeper ranks' rows come from the node rows: a candidate
+// that is no P_{W-1} node has the same row at the end of W-1 as at the end of W-2.
+struct ShallowRows {
+  RowV row[KSG_STAGE];  // rows of candidate ranks < KSG_STAGE (window-start rows)
 };
-__device__ __forceinline__ PriorRec* prior_rec(uint8_t* rec) { return reinterpret_cast<PriorRec*>(rec_rows(rec)); }
-__device__ __forceinline__ const PriorRec* prior_rec(const uint8_t* rec) {
-  return reinterpret_cast<const PriorRec*>(rec_rows(rec));
+__device__ __forceinline__ ShallowRows* shallow_rows(uint8_t* rec) { return reinterpret_cast<ShallowRows*>(rec_rows(rec)); }
+__device__ __forceinline__ const ShallowRows* shallow_rows(const uint8_t* rec) {
+  return reinterpret_cast<const ShallowRows*>(rec_rows(rec));
 }
-static_assert(KSG_BATCH * sizeof(PriorRec) <= kRecKeys * sizeof(RowV), "prior records fit the rows area");
-static_assert(sizeof(PriorRec) % 8 == 0, "8-byte words");
-// The merge of pod b's T tile lists into its candidate record (the pod's
-// last-arriving tile block, or in the persistent loop its merge block): LDS L as
-// win_eval's, h its pod record, pnl / np P_{E-2}'s nodes.
-template <int MODE, bool STAT, bool PER>
-__device__ __forceinline__ void win_merge(const DevCluster& C, const DevProfile& F, const WinArgs& A, uint32_t b, uint64_t* L,
-                                          const PodLite* h, const int32_t* pnl, int np) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  (void)tid;
+static_assert(KSG_BATCH * sizeof(ShallowRows) <= kRecKeys * sizeof(RowV), "shallow rows fit the rows area");
+static_assert(sizeof(ShallowRows) % 8 == 0, "8-byte words");
+// The merge of pod b's T tile lists into its candidate record (by the pod's
+// last-arriving tile block): LDS L as win_eval's, pnl / np P_{E-2}'s nodes.
+template <bool PER>
+__device__ __forceinline__ void win_merge(const DevCluster& C, const WinArgs& A, uint32_t b, uint64_t* L, const int32_t* pnl,
+                                          int np) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   auto pend_lds = [&](int32_t gid) {
     int hit = -1;
     for (int e = 0; e < np; ++e) hit = pnl[e] == gid ? e : hit;
@@ -3944,164 +3919,35 @@ __device__ __forceinline__ void win_merge(const DevCluster& C, const DevProfile&
     if (w < s) L[w * 64 + lane] = wave_merge_top(L[w * 64 + lane], L[(w + s) * 64 + 63 - lane]);
     lds_barrier();
   }
-  if (PER && w == 0) {  // (persistent loop: keys, counts, shallow rows, then the prior step)
+  if (w == 0) {
     const uint64_t v = L[lane];
     const int32_t gid = (int32_t)(v & 0xFFFFFull);
-    PriorRec* pr = prior_rec(A.erec) + b;
-    stv<true>(rec_keys(A.erec) + (size_t)b * KSG_CAND + lane, v);
-    if (lane < KSG_STAGE) {
+    stv<PER>(rec_keys(A.erec) + (size_t)b * KSG_CAND + lane, v);
+    // the candidates' rows: every rank's (sharded: none, they come from the
+    // replica); persistent loop: the shallow ranks', packed per pod
+    if (PER ? lane < KSG_STAGE : !A.xrows) {
       RowV c;
       memset(&c, 0, sizeof(c));
       if (v) {
         const int hh = pend_lds(gid);
-        if (hh >= 0) c = ld_obj<true>(&A.pprev[hh].after);
-        else load_row_p<true>(C, (uint32_t)gid - C.goff, A.need_eph, c);
+        if (hh >= 0) c = ld_obj<PER>(&A.pprev[hh].after);
+        else load_row_p<PER>(C, (uint32_t)gid - C.goff, A.need_eph, c);
       }
-      st_obj<true>(&pr->row[lane], c);
+      st_obj<PER>(PER ? &shallow_rows(A.erec)[b].row[lane] : rec_rows(A.erec) + (size_t)b * KSG_CAND + lane, c);
     }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) f[k] = wave_sum(f[k]);
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) stv<true>(reinterpret_cast<int32_t*>(A.erec) + k * KSG_BATCH + b, f[k]);
-      stv<true>(A.arrive + b * A.astride, 0u);
-    }
-    if (A.evk) {  // (split hand-over) keys, shallow rows and counts are out: the replay may stage them
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0) __hip_atomic_fetch_add(A.evk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // the prior step: pod q on P_{E-1}'s nodes (published by the replay of E-1);
-    // prior_fix: the replay evaluates it itself
-    int np1 = 0;
-    Pend pe;
-    pe.node = -1;
-    if (A.pubw && !A.prior_fix) {
-      uint32_t ok = 1;
-      if (lane == 0) {
-        ok = 0;
-        for (uint32_t it = 0; it < A.spin; ++it) {
-          if (ld_sc1(A.pubw) >= A.pub_need) { ok = 1; break; }
-          if ((it & 63u) == 63u && ld_sc1(A.abortw) != 0u) break;
-          __builtin_amdgcn_s_sleep(2);
-        }
-        if (!ok) __hip_atomic_store(A.abortw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (__builtin_amdgcn_readfirstlane(ok)) {  // (else the run has aborted)
-        // the count and every entry requested together (one round trip, not two)
-        np1 = ldv<true>(A.pcur_n);
-        if (lane < KSG_BATCH) pe = ld_obj<true>(A.pcur + lane);
-      }
-    }
-    if (lane >= np1) pe.node = -1;
-    uint64_t k = 0;
-    if (lane < np1) {
-      int32_t fs, bs;
-      int64_t tot;
-      const uint32_t R = C.R < 4 ? C.R : 4;
-      StaticRec sr{KSG_FILTER_PASS, 0};
-      uint32_t code;
-      int64_t mt = 0, ma = 0;
-      if (STAT) {  // (the static maxima and records were computed before the launch)
-        const uint32_t q = A.e0 + b;
-        mt = ldv<PER>(A.mpred + 2 * (q - A.first));
-        ma = ldv<PER>(A.mpred + 2 * (q - A.first) + 1);
-        sr = srec_at<PER>(A, q, (uint32_t)pe.node);
-        code = eval_row_s<MODE>(pe.after, F, h, R, sr, mt, ma, fs, bs, tot);
-      } else {
-        code = eval_row<MODE>(pe.after, F, h, R, fs, bs, tot);
-      }
-      const bool snap_ok = sr.code == KSG_FILTER_PASS && (F.pos_fit < 0 || fit_filter_row(pe.base, h, R) == 0);
-      PatchV pt;
-      pt.code = code;
-      pt.fitba = fs | (bs << 16);
-      pt.total = (int32_t)tot;
-      pt.raw = sr.raw;
-      k = code == KSG_FILTER_PASS ? pack_key(tot, F.seed, h->queue_idx, (uint32_t)pe.node) : 0;
-      stv<true>(&pr->pkey[lane], k);
-      st_obj<true>(&pr->patch[lane], pt);
-      const int df = (code == KSG_FILTER_PASS ? 1 : 0) - (snap_ok ? 1 : 0);
-      int dT = 0, dA = 0;
-      if (STAT) {
-        const bool na_on = F.pos_na >= 0 && !(h->flags & KPF_SKIP_NA_SCORE);
-        dT = F.pos_taint >= 0 && (int64_t)(sr.raw >> 20) == mt ? df : 0;
-        dA = na_on && (int64_t)(sr.raw & KSG_RAW_NA_MASK) == ma ? df : 0;
-      }
-      stv<true>(&pr->pdf[lane], (int32_t)(((uint32_t)df & 0xFFu) | (((uint32_t)dT & 0xFFu) << 8) | (((uint32_t)dA & 0xFFu) << 16)));
-    }
-    bool isp = false;  // candidate `lane` is a P_{E-1} node
-    for (int e = 0; e < np1; ++e) isp |= v != 0 && __builtin_amdgcn_readlane(pe.node, e) == gid;
-    const unsigned long long pm = __ballot(isp);
-    const uint64_t kb = wave_max(k);
-    const unsigned long long mb = __ballot(kb != 0 && k == kb);
-    if (lane == 0) {
-      if (!A.prior_fix) {
-        stv<true>(&pr->pmask, (uint64_t)pm);
-        stv<true>(&pr->pbest, kb);
-        stv<true>(&pr->pbest_e, (int32_t)(mb ? __ffsll((long long)mb) - 1 : -1));
-        stv<true>(&pr->np, np1);
-      }
-      if (A.estamps) atomicMax((unsigned long long*)&A.estamps[10], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the pod's record is out (wave 0 stored all of it)
-    if (lane == 0) __hip_atomic_fetch_add(A.evd, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else if (w == 0) {
-    uint64_t v = L[lane];
-    RowV c;
-    memset(&c, 0, sizeof(c));
-    int32_t gid = (int32_t)(v & 0xFFFFFull);
-    int hh = pend_lds(gid);
-    if (v) {
-      if (hh >= 0) c = ld_obj<PER>(&A.pprev[hh].after);
-      else load_row_p<PER>(C, (uint32_t)gid - C.goff, A.need_eph, c);
-    }
-    stv<PER>(rec_keys(A.erec) + (size_t)b * KSG_CAND + lane, v);
-    if (!A.xrows) st_obj<PER>(rec_rows(A.erec) + (size_t)b * KSG_CAND + lane, c);  // (sharded: rows from the replica)
 #pragma unroll
     for (int k = 0; k < 3; ++k) f[k] = wave_sum(f[k]);
     if (lane == 0) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) stv<PER>(reinterpret_cast<int32_t*>(A.erec) + k * KSG_BATCH + b, f[k]);
       stv<PER>(A.arrive + b * A.astride, 0u);
-      if (A.estamps) atomicMax((unsigned long long*)&A.estamps[10], (unsigned long long)__builtin_amdgcn_s_memrealtime());
     }
     if constexpr (PER) {  // the pod's record is out (wave 0 stored all of it): the replay may stage it
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if (lane == 0) __hip_atomic_fetch_add(A.evd, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    if (lane == 0 && A.estamps) atomicMax((unsigned long long*)&A.estamps[10], (unsigned long long)__builtin_amdgcn_s_memrealtime());
   }
-}
-// Persistent loop, dedicated merge block of pod b: waits for the pod's T tile
-// lists (the arrival counter), then merges them (win_merge) while the tile blocks
-// go on to the next window.
-template <int MODE, bool STAT = false>
-__device__ __forceinline__ bool win_merge_block(const DevCluster& C, const DevProfile& F, const WinArgs& A, uint32_t b,
-                                                uint64_t* L) {
-  const int tid = threadIdx.x;
-  uint32_t* wcount = reinterpret_cast<uint32_t*>(L + 16 * 64);
-  PodLite* h = reinterpret_cast<PodLite*>(wcount + 96);
-  int32_t* pnl = reinterpret_cast<int32_t*>(wcount + 64);
-  const uint32_t q = A.e0 + b;
-  constexpr int kPodW = (int)(sizeof(PodLite) / 8);
-  if (tid < kPodW) reinterpret_cast<uint64_t*>(h)[tid] = reinterpret_cast<const uint64_t*>(A.plite + q)[tid];
-  if (tid == 0) {
-    bool ok = false;
-    for (uint32_t it = 0; it < A.spin; ++it) {
-      if (ld_sc1(A.arrive + b * A.astride) >= A.T) { ok = true; break; }
-      if ((it & 63u) == 63u && ld_sc1(A.abortw) != 0u) break;
-      __builtin_amdgcn_s_sleep(4);
-    }
-    if (!ok) __hip_atomic_store(A.abortw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    wcount[17] = ok ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!wcount[17]) return false;
-  // P_{E-2} only now: the tiles arrived, so their blocks saw it published (a merge
-  // block may otherwise run a window ahead of the replay that writes it)
-  const int np = ldv<true>(A.pprev_n);
-  if (tid < np) pnl[tid] = ldv<true>(&A.pprev[tid].node);
-  __syncthreads();
-  win_merge<MODE, STAT, true>(C, F, A, b, L, h, pnl, np);
-  return true;
 }
 // Blocks 1.. of k_window: one pod x KSG_TILE nodes per block.  Tile lists are
 // handed to the pod's last-arriving block with sc1 stores/loads and an agent
@@ -4253,7 +4099,7 @@ __device__ __forceinline__ void win_eval(const DevCluster& C, const DevProfile& 
     uint32_t old = 0;
     if (lane == 0) old = __hip_atomic_fetch_add(A.arrive + b * A.astride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     old = __builtin_amdgcn_readfirstlane(old);
-    if (lane == 0) wcount[16] = (!A.mblocks && old == A.T - 1) ? 1u : 0u;  // (slots 17..31 unused)
+    if (lane == 0) wcount[16] = old == A.T - 1 ? 1u : 0u;  // (slots 17..31 unused)
   }
   auto flush_stash = [&]() {
     if (!stash_all && w != 0) return;
@@ -4300,7 +4146,7 @@ __device__ __forceinline__ void win_eval(const DevCluster& C, const DevProfile& 
     signal_flushed();
     return;
   }
-  win_merge<MODE, STAT, PER>(C, F, A, b, L, h, pnl, np);
+  win_merge<PER>(C, A, b, L, pnl, np);
   flush_stash();
   signal_flushed();
 }
@@ -4643,26 +4489,7 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
   const uint64_t* rows = reinterpret_cast<const uint64_t*>(rec_rows(A.wrec));
   const int nk = nb * KSG_CAND, nr = nb * KSG_STAGE * kRowW;
   uint64_t kv[2], rv[6];
-  // (persistent loop) the prior step the eval blocks did: thread = (pod, prior entry)
-  const int ppb = tid >> 5, ppe = tid & 31;
-  const PriorRec* PR = prior_rec(A.wrec);
-  uint64_t pr_k = 0, pr_p0 = 0, pr_p1 = 0, pr_m = 0;
-  int32_t pr_df = 0;
-  const bool prior_rec_in = PER && !A.prior_fix;  // (else the prior step is evaluated below)
-  const bool pr_late = prior_rec_in && A.evd_wait != nullptr;  // (split: after the keys and rows are requested)
-  auto prior_loads = [&]() {
-    if (ppb < nb) {
-      pr_k = ldv<true>(&PR[ppb].pkey[ppe]);
-      const uint64_t* pw = reinterpret_cast<const uint64_t*>(&PR[ppb].patch[ppe]);
-      pr_p0 = ldv<true>(pw);
-      pr_p1 = ldv<true>(pw + 1);
-      pr_df = ldv<true>(&PR[ppb].pdf[ppe]);
-      if (ppe == 0) pr_m = ldv<true>(&PR[ppb].pmask);
-      if (ppe == 1) pr_m = ldv<true>(&PR[ppb].pbest);
-      if (ppe == 2) pr_m = (uint64_t)(uint32_t)ldv<true>(&PR[ppb].pbest_e);
-    }
-  };
-  if (prior_rec_in && !pr_late) prior_loads();
+  const ShallowRows* SR = shallow_rows(A.wrec);  // (persistent loop)
   {
     if (!p_late) p_list_load();
     constexpr int kPodW = (int)(sizeof(PodLite) / 8);
@@ -4686,7 +4513,7 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
       int i = tid + k * KSG_WIN_THREADS;
       int row = i / kRowW, wd = i - row * kRowW;
       int p = row / KSG_STAGE, r = row - p * KSG_STAGE;
-      if constexpr (PER) rv[k] = i < nr ? ldv<true>(reinterpret_cast<const uint64_t*>(&PR[p].row[r]) + wd) : 0;
+      if constexpr (PER) rv[k] = i < nr ? ldv<true>(reinterpret_cast<const uint64_t*>(&SR[p].row[r]) + wd) : 0;
       else rv[k] = i < nr ? rows[(size_t)(p * KSG_CAND + r) * kRowW + wd] : 0;
     }
     auto small_stores = [&]() {  // what P_{W-1} does not enter: pods, counts, cleared picks
@@ -4709,38 +4536,23 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
       }
     };
     if (p_late) small_stores();  // (ahead of the wait; the keys and rows stay in registers across it)
-    if (pr_late || p_late) {
+    if (p_late) {
       // the keys and rows are in flight: wait for the other block's publish of W-1
-      // (two replay blocks), then for the window's prior steps; then P_{W-1} and
-      // the prior records
+      // (two replay blocks), then P_{W-1}
       if (tid == 0) {
-        bool ok = true;
-        if (p_late) {
-          ok = false;
-          if (A.rstamps) A.rstamps[0] = __builtin_amdgcn_s_memrealtime();
-          for (uint32_t it = 0; it < A.spin; ++it) {
-            if (ld_sc1(A.pub_wait) >= A.pub_wait_need) { ok = true; break; }
-            if ((it & 63u) == 63u && ld_sc1(A.abortw) != 0u) break;
-            __builtin_amdgcn_s_sleep(1);
-          }
-          if (A.rstamps) A.rstamps[1] = __builtin_amdgcn_s_memrealtime();
+        bool ok = false;
+        if (A.rstamps) A.rstamps[0] = __builtin_amdgcn_s_memrealtime();
+        for (uint32_t it = 0; it < A.spin; ++it) {
+          if (ld_sc1(A.pub_wait) >= A.pub_wait_need) { ok = true; break; }
+          if ((it & 63u) == 63u && ld_sc1(A.abortw) != 0u) break;
+          __builtin_amdgcn_s_sleep(1);
         }
-        if (ok && pr_late) {
-          ok = false;
-          for (uint32_t it = 0; it < A.spin; ++it) {
-            if (ld_sc1(A.evd_wait) >= A.evd_need) { ok = true; break; }
-            if ((it & 63u) == 63u && ld_sc1(A.abortw) != 0u) break;
-            __builtin_amdgcn_s_sleep(1);
-          }
-        }
+        if (A.rstamps) A.rstamps[1] = __builtin_amdgcn_s_memrealtime();
         if (!ok) __hip_atomic_store(A.abortw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       lds_barrier();  // (no fence: the previous window's patch stores stay in flight)
-      if (p_late) {
-        p_loads();
-        p_list_load();
-      }
-      if (pr_late) prior_loads();
+      p_loads();
+      p_list_load();
     }
     if (tid < np * kPendW) reinterpret_cast<uint64_t*>(L.prior)[tid] = pv;
     if (!p_late) small_stores();
@@ -4759,22 +4571,7 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
     if ((uint32_t)pe.node >= C.goff && nl < C.N) store_row_p<PER>(C, nl, pe.after);
     if (A.xrows) A.xrows[pe.node] = pe.after;  // every rank's replica, every node
   }
-  if (prior_rec_in) {  // the eval blocks' prior step, staged
-    if (ppb < nb) {
-      L.pkey[ppb][ppe] = pr_k;
-      reinterpret_cast<uint64_t*>(&L.patch[ppb][ppe])[0] = pr_p0;
-      reinterpret_cast<uint64_t*>(&L.patch[ppb][ppe])[1] = pr_p1;
-      L.pdf[ppb][ppe] = (int8_t)(pr_df & 0xFF);
-      if (STAT) {
-        L.pdfT[ppb][ppe] = (int8_t)((pr_df >> 8) & 0xFF);
-        L.pdfA[ppb][ppe] = (int8_t)((pr_df >> 16) & 0xFF);
-      }
-      if (ppe == 0) L.pmask[ppb] = pr_m;
-      if (ppe == 1) L.pbest[ppb] = pr_m;
-      if (ppe == 2) L.pbest_e[ppb] = (int32_t)(uint32_t)pr_m;
-    }
-    STAMP(16);
-  } else {  // pods on the P_{W-1} nodes as of the window start (independent of the picks)
+  {  // the prior step: pods on the P_{W-1} nodes as of the window start (independent of the picks)
     const int pb = 2 * wave + (lane >> 5), e = lane & 31;
     uint64_t k = 0;
     if (pb < nb && e < np) {
@@ -4828,11 +4625,9 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
     int i = tid + k * KSG_WIN_THREADS;
     if (i < nk) (&L.key[0][0])[i] = kv[k];
     const int b = wave + 16 * k;
-    if (!prior_rec_in) {  // (PriorRec: the eval blocks' pmask)
-      bool m = kv[k] != 0 && np > 0 && prior_of(L, (int32_t)(kv[k] & 0xFFFFFull)) >= 0;
-      unsigned long long mask = __ballot(m);
-      if (lane == 0 && b < nb) L.pmask[b] = mask;
-    }
+    bool m = kv[k] != 0 && np > 0 && prior_of(L, (int32_t)(kv[k] & 0xFFFFFull)) >= 0;
+    unsigned long long mask = __ballot(m);
+    if (lane == 0 && b < nb) L.pmask[b] = mask;
   }
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
@@ -5261,9 +5056,10 @@ __global__ void k_rows_unpack(const RowV* recv, uint32_t ranks, uint32_t G, uint
 // boundaries of k_window become hand-offs (agent-scope counters, sc1 data):
 //   eval(E)   starts once replay(E-2) is published (Z.replayed >= E-1): the rows as of
 //             the end of window E-2 (P_{E-2} from its list) — as k_window's eval part;
-//   replay(W) starts once every pod of window W has its candidate record (Z.evd),
-//             and writes its output patches once every eval block of W wrote its
-//             outputs (Z.flushed);
+//   replay(W) starts once every pod of window W has its candidate record (Z.evd:
+//             the merge's keys, shallow rows and counts; the replay evaluates the
+//             pods on P_{W-1} itself, as k_window's does), and writes its output
+//             patches once every eval block of W wrote its outputs (Z.flushed);
 // and the buffers of window parity p (tile lists, records, arrivals, P lists,
 // output ring) are reused two windows later, after those waits.  A launch whose
 // blocks are not all resident leaves at the handshake (run_handshake) and the
@@ -5274,10 +5070,9 @@ __global__ void k_rows_unpack(const RowV* recv, uint32_t ranks, uint32_t G, uint
 // window to window (nxt_ok is per block and refers to the block's next window,
 // W+2), so the only new ordering is between replay(W-1) and replay(W):
 //   replay(W), W >= 1, waits for Z.replayed >= W (one replica, sc1) before it reads
-//             P_{W-1} (pend[(W-1)&1]) and, after that, polls Z.evd for the prior
-//             records.  What does not depend on P_{W-1} — the wait for the keys
-//             (Z.evk), the key and row loads (held in registers), pods, feasible
-//             counts, cleared tables — is done before that wait.
+//             P_{W-1} (pend[(W-1)&1]).  What does not depend on P_{W-1} — the wait
+//             for the records (Z.evd), the key and row loads (held in registers),
+//             pods, feasible counts, cleared tables — is done before that wait.
 //   The publish of W-1 follows vmcnt(0) and a barrier of its block, so by then
 //             P_{W-2} is written back to the node rows and P_{W-1} is complete in
 //             pend[(W-1)&1]; replay(W) reads nothing else replay(W-1) wrote.  The
@@ -5287,7 +5082,7 @@ __global__ void k_rows_unpack(const RowV* recv, uint32_t ranks, uint32_t G, uint
 //             replay(W) overwrites with P_{W-1} — with two blocks it runs before
 //             the publish (win_fixup).
 //   pend[W&1] held P_{W-2}; replay(W) overwrites it with P_W after Z.evd(W) (so
-//             the evaluation and prior steps of W, which read it, are done) and
+//             the evaluation and merges of W, which read it, are done) and
 //             after the publish of W-1 (whose replay read P_{W-2} into LDS before).
 //   wrec[W&1] is read by replay(W) only before its publish, and rewritten by the
 //             evaluation of W+2 only after it: as with one block.
@@ -5301,8 +5096,6 @@ struct WinSync {
   uint32_t pad1[30];
   uint32_t flushed[2];    // per window parity: eval blocks whose outputs are written (cumulative)
   uint32_t pad2[30];
-  uint32_t evk[2];        // per window parity: pods whose keys and shallow rows are out (split hand-over)
-  uint32_t pad3[30];
 };
 struct WinRunArgs {
   uint32_t nwin, first, count, T;
@@ -5398,20 +5191,15 @@ __global__ __launch_bounds__(KSG_WIN_THREADS) void k_window_run(DevCluster C, De
       // parity is whole, KSG_BATCH pods)
       A.flushed = &Z->flushed[W & 1];
       A.flush_need = ((W >> 1) * KSG_BATCH + A.nw) * R.T;
-      // (split: the keys counter gates the stage, the records counter the PriorRec reads;
-      // `ready` then refers to the keys counter)
       const uint32_t need = (W >> 1) * KSG_BATCH + A.nw;
-      const bool split = A0.split && !A0.prior_fix;
       // (diagnostic stamps past the windows' slots: loop top, ready, after the wait)
       uint64_t* const lt = R.stamps ? R.stamps + (size_t)R.nwin * 32 + (size_t)W * 4 : nullptr;
       if (lt && threadIdx.x == 0) {
         lt[0] = __builtin_amdgcn_s_memrealtime();
         lt[1] = ready ? 1u : 0u;
       }
-      if (!ready && !win_wait_ge<false>(split ? &Z->evk[W & 1] : &Z->evd[W & 1], need, abortw, RC.spin, &go)) return;
+      if (!ready && !win_wait_ge<false>(&Z->evd[W & 1], need, abortw, RC.spin, &go)) return;
       if (lt && threadIdx.x == 0) lt[2] = __builtin_amdgcn_s_memrealtime();
-      A.evd_wait = split ? &Z->evd[W & 1] : nullptr;
-      A.evd_need = need;
       A.pub = &Z->replayed[0][0];
       A.pub_val = W + 1;
       // (two replay blocks: P_{W-1} and the node rows under it are the other block's)
@@ -5420,7 +5208,7 @@ __global__ __launch_bounds__(KSG_WIN_THREADS) void k_window_run(DevCluster C, De
       A.rstamps = R.stamps ? R.stamps + (size_t)R.nwin * 36 + (size_t)W * 4 : nullptr;
       if (W + nrep < R.nwin) {  // (this block's next window)
         const uint32_t w1 = W + nrep, nw1 = min((uint32_t)KSG_BATCH, R.first + R.count - (R.first + w1 * KSG_BATCH));
-        A.nxt_evd = split ? &Z->evk[w1 & 1] : &Z->evd[w1 & 1];
+        A.nxt_evd = &Z->evd[w1 & 1];
         A.nxt_need = (w1 >> 1) * KSG_BATCH + nw1;
       } else {
         A.nxt_evd = nullptr;
@@ -5431,31 +5219,6 @@ __global__ __launch_bounds__(KSG_WIN_THREADS) void k_window_run(DevCluster C, De
     return;
   }
   uint64_t* const L = reinterpret_cast<uint64_t*>(lds_raw);
-  if (A0.mblocks && blockIdx.x >= nrep + KSG_BATCH * R.T) {  // the merge block of pod b
-    const uint32_t b = blockIdx.x - nrep - KSG_BATCH * R.T;
-    for (uint32_t E = 0; E < R.nwin; ++E) {
-      A.nw = 0;
-      A.e0 = R.first + E * KSG_BATCH;
-      A.ne = min((uint32_t)KSG_BATCH, R.first + R.count - A.e0);
-      if (b >= A.ne) break;
-      A.tile_top = R.tile_top + (size_t)(E & 1) * R.tt_sz;
-      A.tile_feas = R.tfeas + (size_t)(E & 1) * R.tf_sz;
-      A.erec = R.wrec + (size_t)(E & 1) * kRecBytes;
-      A.pprev = R.pend + (size_t)(E & 1) * KSG_BATCH;  // P_{E-2}
-      A.pprev_n = R.pend_n + (E & 1);
-      A.arrive = R.arrive + (size_t)(E & 1) * KSG_BATCH * 32;
-      A.estamps = R.stamps ? R.stamps + (size_t)E * 32 : nullptr;
-      A.evd = &Z->evd[E & 1];
-      A.evk = A0.split && !A0.prior_fix ? &Z->evk[E & 1] : nullptr;
-      A.pcur = R.pend + (size_t)((E + 1) & 1) * KSG_BATCH;  // P_{E-1}
-      A.pcur_n = R.pend_n + ((E + 1) & 1);
-      A.pubw = E >= 1 ? &Z->replayed[b & 15][0] : nullptr;
-      A.pub_need = E;
-      if (!win_merge_block<MODE, STAT>(C, F, A, b, L)) return;
-      __syncthreads();  // (LDS reused by the next window)
-    }
-    return;
-  }
   const uint32_t blk = blockIdx.x - nrep, b = blk / R.T;
   for (uint32_t E = 0; E < R.nwin; ++E) {
     A.nw = 0;
@@ -5471,12 +5234,7 @@ __global__ __launch_bounds__(KSG_WIN_THREADS) void k_window_run(DevCluster C, De
     A.arrive = R.arrive + (size_t)(E & 1) * KSG_BATCH * 32;
     A.estamps = R.stamps ? R.stamps + (size_t)E * 32 : nullptr;
     A.evd = &Z->evd[E & 1];
-    A.evk = A0.split && !A0.prior_fix ? &Z->evk[E & 1] : nullptr;
     A.flushed = &Z->flushed[E & 1];
-    A.pcur = R.pend + (size_t)((E + 1) & 1) * KSG_BATCH;  // P_{E-1}
-    A.pcur_n = R.pend_n + ((E + 1) & 1);
-    A.pubw = E >= 1 ? &Z->replayed[blk & 15][0] : nullptr;  // (E = 0: P_{-1} is empty)
-    A.pub_need = E;
     if (STAT && R.sready && !win_stat_gate(R, A.e0 - R.first, A.ne, abortw, RC.spin, &go)) return;
     win_eval<MODE, STAT, true>(C, F, A, blk, L);
     __syncthreads();  // (LDS reused by the next window)
@@ -5703,9 +5461,8 @@ struct Engine::Impl {
                                  // a failing synchronisation then leaves host mirror and device apart (lost)
   DBuf<WinSync> wsync;           // k_window_run's counters (zeroed per launch)
   int win_run_on = 1;            // persistent window loop (k_window_run): KSG_WIN_RUN=0 turns it off
-  int win_mblocks = 0;           // ... with dedicated merge blocks (KSG_WIN_MB=1; the last tile block merges: measured faster)
-  int win_replay2 = 1;           // ... two replay blocks, even / odd windows (KSG_WIN_REPLAY2; measured faster with
-                                 // KSG_WIN_PFIX=1 on Fit / BalancedAllocation profiles, slower on static ones)
+  int win_replay2 = 1;           // ... two replay blocks, even / odd windows (KSG_WIN_REPLAY2; measured faster on
+                                 // Fit / BalancedAllocation profiles, slower on static ones)
   int win_replay2_stat = 0;      // ... the same for Taint / NodeAffinity profiles
   int view_copy = 0;             // cycle view: 1 = the per-node arrays by a copy (KSG_VIEW_COPY), 0 = written by k_view
   int view_fuse = 1;             // fused views (Engine::view_arm; KSG_VIEW_FUSE=0: k_view always)
@@ -5717,9 +5474,6 @@ struct Engine::Impl {
   uint8_t* vp_hout = nullptr;
   int run_overlap = 0;           // k_chain_run: pod k+1's class-table reads during pod k's hand-offs (KSG_RUN_OVERLAP=1; measured no faster)
   int run_defer = 1;             // k_chain_run: the owner's independent node-level assume deferred (KSG_RUN_DEFER=0: off)
-  int win_split = 1;             // ... split hand-over: keys staged while the prior steps run (KSG_WIN_SPLIT=0: one counter)
-  int win_pfix = -1;             // ... the replay evaluates the prior step itself (KSG_WIN_PFIX=1) or the merges do (0);
-                                 // unset: as measured — the replay on static profiles and with two replay blocks
   uint64_t win_runs = 0, win_fallbacks = 0;  // diagnostic: persistent window launches / not co-resident
   uint32_t fold_blocks = 256;  // table chain: k_fold above this many blocks (KSG_FOLD_BLOCKS; tests force it)
   uint32_t occ_blocks = 0;     // table chain: occupancy twins above this many blocks (0: 2 per CU; KSG_OCC_BLOCKS)
@@ -5902,10 +5656,7 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
   if (const char* e = std::getenv("KSG_RUN_LAG")) I.run_lag = std::min<uint32_t>(4096, (uint32_t)std::strtoul(e, nullptr, 10));
   if (const char* e = std::getenv("KSG_RUN_NORES")) I.run_need_extra = std::strtol(e, nullptr, 10) != 0 ? 1u : 0u;
   if (const char* e = std::getenv("KSG_WIN_RUN")) I.win_run_on = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_WIN_MB")) I.win_mblocks = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_WIN_PFIX")) I.win_pfix = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_WIN_REPLAY2")) I.win_replay2 = I.win_replay2_stat = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_WIN_SPLIT")) I.win_split = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_RUN_OVERLAP")) I.run_overlap = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_RUN_DEFER")) I.run_defer = (int)std::strtol(e, nullptr, 10);
   if (const char* e = std::getenv("KSG_VIEW_COPY")) I.view_copy = (int)std::strtol(e, nullptr, 10);
@@ -6488,12 +6239,10 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
   // the persistent window loop: one launch for every window (its blocks all
   // resident: one per CU); not co-resident -> the launch-per-window loop below
   if (persist_ok && (!stat || stat_run)) {
-    // dedicated merge blocks (one per pod) when they fit beside the tile blocks
     // (two replay blocks when the extra block fits as well)
     const bool r2 = (stat ? I.win_replay2_stat : I.win_replay2) && 2 + (uint64_t)KSG_BATCH * T <= I.n_cus;
     const uint32_t nrep = r2 ? 2u : 1u;
-    const bool mb = I.win_mblocks && nrep + (uint64_t)KSG_BATCH * (T + 1) <= I.n_cus;
-    const uint32_t grid = nrep + KSG_BATCH * T + (mb ? KSG_BATCH : 0);
+    const uint32_t grid = nrep + KSG_BATCH * T;
     // the run's records: before the launch, or (KSG_STATIC_OVERLAP, default)
     // beside it — k_static_dec_run, one 1,024-thread block per CU the loop leaves
     // idle, launched on the side stream BEFORE the loop (its blocks then hold
@@ -6561,11 +6310,8 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
     R.sready = overlap ? I.sready.p : nullptr;
     R.sready_need = std::max<uint32_t>((SN + 1024 * KSG_SD_NPT - 1) / (1024 * KSG_SD_NPT), 1);  // (k_static_dec_run's node tiles)
     WinArgs AP = A;
-    AP.mblocks = mb ? 1u : 0u;
     AP.astride = 32;
-    AP.prior_fix = (I.win_pfix >= 0 ? I.win_pfix != 0 : (stat || r2)) ? 1u : 0u;
     AP.replay2 = r2 ? 1u : 0u;
-    AP.split = I.win_split ? 1u : 0u;
     __atomic_store_n(I.hverdict, 0u, __ATOMIC_RELEASE);
     RunCtl RC{grid + I.run_need_extra, I.run_wait_us * 100u, 0, I.hverdict, I.run_spin};
     if (overlap) {

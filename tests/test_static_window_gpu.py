@@ -133,10 +133,8 @@ def test_static_records_decoded_and_walked(monkeypatch, dec):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env", [{}, {"KSG_STATIC_OVERLAP": "0"}, {"KSG_STATIC_RUN_MB": "0"}, {"KSG_WIN_MB": "1"},
-                                 {"KSG_WIN_PFIX": "1"}, {"KSG_WIN_SPLIT": "0"}],
-                         ids=["persistent", "records-before", "per-window", "merge-blocks", "prior-in-replay",
-                              "one-counter"])
+@pytest.mark.parametrize("env", [{}, {"KSG_STATIC_OVERLAP": "0"}, {"KSG_STATIC_RUN_MB": "0"}, {"KSG_WIN_REPLAY2": "1"}],
+                         ids=["persistent", "records-before", "per-window", "two-replay-blocks"])
 def test_static_profiles_persistent_window_loop(monkeypatch, env):
     """Taint / NodeAffinity profiles in the persistent window loop (k_window_run;
     its static records computed by k_static_dec beside the loop, each window's
