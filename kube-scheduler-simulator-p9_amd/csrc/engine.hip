@@ -432,6 +432,24 @@ __device__ __forceinline__ int64_t div_small(int64_t x, int64_t a) {
   else if ((q + 1) * a <= x) q++;
   return q;
 }
+__device__ __forceinline__ int64_t least_req(int64_t a, int64_t q) {  // leastRequestedScore
+  return q > a ? 0 : div_small((a - q) * 100, a);
+}
+// leastRequestedScore for the compiled default arguments: floor((a-q)*100/a)
+// from one f64 reciprocal estimate (relative error near 2^-28, quotient <= 100,
+// so the truncated estimate is the quotient or one beside it) and one exact
+// integer correction, branch-free.  Exact wherever x = (a-q)*100 fits int64
+// (0 <= q, a < 2^56): the conversions of x and a round by 2^-53, far inside the
+// estimate's own error, d <= 101 keeps d*a in int64, and the remainder is an
+// integer difference.  (A 2^52 gate to the 64-bit divide stood here; no operand
+// told the two apart, so it went.)
+__device__ __forceinline__ int64_t least_req_q(int64_t a, int64_t q) {
+  if (q > a || a <= 0) return 0;
+  int64_t x = (a - q) * 100;
+  int64_t d = (int64_t)((double)x * __builtin_amdgcn_rcp((double)a));
+  int64_t rem = x - d * a;
+  return rem >= a ? d + 1 : (rem < 0 ? d - 1 : d);
+}
 // floor(x / d) for x < 2^27, 1 <= d, quotient <= 128: one f32 reciprocal
 // estimate (error well below 1) and one exact correction either way.
 __device__ __forceinline__ uint32_t udiv_small(uint32_t x, uint32_t d) {
@@ -442,8 +460,8 @@ __device__ __forceinline__ uint32_t udiv_small(uint32_t x, uint32_t d) {
 __device__ __forceinline__ bool lane0() { return (threadIdx.x & 63) == 0; }
 
 // BalancedAllocation's float64 steps (balanced_allocation.go balancedResourceScorer),
-// one Go operation each, shared by every restatement of the plugin below and by
-// k_selftest_arith: the fraction min(requested / allocatable, 1), the two-resource
+// one Go operation each, shared by ba_walk, ba_score's two-resource fast path and
+// the what-if class path: the fraction min(requested / allocatable, 1), the two-resource
 // deviation |f0 - f1| / 2, one squared deviation and the root of their mean for
 // more resources, and the score int64((1 - std) * 100).
 __device__ __forceinline__ double ba_frac(int64_t q, int64_t a) {
@@ -576,26 +594,91 @@ __device__ uint32_t volume_filter(const DevCluster& C, const ProgView& V, int po
   return bits ? ((uint32_t)sub << 16) | bits : 0u;
 }
 
-__device__ __forceinline__ uint32_t fit_filter(const DevCluster& C, const ProgView& V, uint32_t n) {
+__device__ int64_t rtc_fn(const DevProfile& F, int64_t p);
+__device__ __noinline__ int64_t rtc_fn_ool(const DevProfile& F, int64_t p);
+__device__ __forceinline__ int64_t sel4(const int64_t (&v)[4], int i) {
+  return i == 0 ? v[0] : i == 1 ? v[1] : i == 2 ? v[2] : v[3];
+}
+struct RowV {  // one node row (resource columns 0..3)
+  int64_t alloc[4], req[4];
+  int64_t nzc, nzm;
+  int32_t podcnt, allowed;
+};
+// Operand sources of NodeResourcesFit and BalancedAllocation: where a node's
+// quantities come from.  The plugin bodies below are written once over a source;
+// what differs between the kernels that score on the node columns and the ones
+// that score on a RowV is a member here (DESIGN.md "Where each plugin is stated"):
+// the resource / weight tables (kernel-argument arrays against device memory:
+// the row kernels' SGPRs), the RequestedToCapacityRatio shape function in line
+// against out of line (the row kernels' registers), that ratio's quotient, and when
+// a weight is read (kWeightFirst; at its use it stays out of the column kernels' SGPRs).
+struct ColSrc {  // the columns of DevCluster at node n: every resource column
+  const DevCluster& C;
+  uint32_t n;
+  static constexpr bool kWeightFirst = false;
+  __device__ __forceinline__ int64_t allocatable(int res) const { return C.alloc[(size_t)res * C.N + n]; }
+  __device__ __forceinline__ int64_t requested(int res) const { return C.req[(size_t)res * C.N + n]; }
+  __device__ __forceinline__ int64_t nz_cpu() const { return C.nzc[n]; }
+  __device__ __forceinline__ int64_t nz_mem() const { return C.nzm[n]; }
+  __device__ __forceinline__ int32_t podcnt() const { return C.podcnt[n]; }
+  __device__ __forceinline__ int32_t allowed() const { return C.allowed[n]; }
+  static __device__ __forceinline__ int fit_res(const DevProfile& F, int i) { return F.fit_res[i]; }
+  static __device__ __forceinline__ int64_t fit_w(const DevProfile& F, int i) { return F.fit_w[i]; }
+  static __device__ __forceinline__ int ba_res(const DevProfile& F, int i) { return F.ba_res[i]; }
+  static __device__ __forceinline__ int64_t rtc(const DevProfile& F, int64_t p) { return rtc_fn(F, p); }
+  static __device__ __forceinline__ int64_t rtc_util(int64_t q, int64_t a) { return q * 100 / a; }
+};
+struct RowSrc {  // a RowV: resource columns 0..3, cpu and memory always (load_row)
+  const RowV& r;
+  static constexpr bool kWeightFirst = true;
+  __device__ __forceinline__ int64_t allocatable(int res) const { return sel4(r.alloc, res); }
+  __device__ __forceinline__ int64_t requested(int res) const { return sel4(r.req, res); }
+  __device__ __forceinline__ int64_t nz_cpu() const { return r.nzc; }
+  __device__ __forceinline__ int64_t nz_mem() const { return r.nzm; }
+  __device__ __forceinline__ int32_t podcnt() const { return r.podcnt; }
+  __device__ __forceinline__ int32_t allowed() const { return r.allowed; }
+  static __device__ __forceinline__ int fit_res(const DevProfile& F, int i) { return F.fit_res_d[i]; }
+  static __device__ __forceinline__ int64_t fit_w(const DevProfile& F, int i) { return F.fit_w_d[i]; }
+  static __device__ __forceinline__ int ba_res(const DevProfile& F, int i) { return F.ba_res_d[i]; }
+  static __device__ __forceinline__ int64_t rtc(const DevProfile& F, int64_t p) { return rtc_fn_ool(F, p); }
+  static __device__ __forceinline__ int64_t rtc_util(int64_t q, int64_t a) { return div_small(q * 100, a); }
+};
+
+// NodeResourcesFit Filter (fit.go fitsRequest) of pod program header h (ksg_prog
+// or a decoded pod) on R resource columns: reason bits, 0 = fits.
+template <class S, class P>
+__device__ __forceinline__ uint32_t fit_filter(const S& s, const P* h, uint32_t R) {
   uint32_t bits = 0;
-  if (C.podcnt[n] + 1 > C.allowed[n]) bits |= KSG_FIT_TOO_MANY_PODS;
-  if (V.h->flags & KPF_ZERO_REQUEST) return bits;
-  for (uint32_t r = 0; r < C.R; ++r) {
-    int64_t q = V.h->req[r];
-    if (q <= 0) continue;  // cpu/mem/eph: "> 0" guard; scalars: zero skipped
-    if (q > C.alloc[(size_t)r * C.N + n] - C.req[(size_t)r * C.N + n]) bits |= 1u << (1 + r);
+  if (s.podcnt() + 1 > s.allowed()) bits |= KSG_FIT_TOO_MANY_PODS;
+  if (h->flags & KPF_ZERO_REQUEST) return bits;
+  for (uint32_t r = 0; r < R; ++r) {
+    const int64_t q = h->req[r];  // cpu/mem/eph: "> 0" guard; scalars: zero skipped
+    if (q > 0 && q > s.allocatable((int)r) - s.requested((int)r)) bits |= 1u << (1 + r);
   }
   return bits;
 }
 
-// resourceAllocationScorer.calculateResourceAllocatableRequest
-__device__ __forceinline__ void alloc_req(const DevCluster& C, uint32_t n, int res, int64_t pod_req, bool use_requested,
-                                          int64_t& a, int64_t& q) {
+// resourceAllocationScorer.calculateResourceAllocatableRequest, stated per source:
+// as one template over allocatable() / requested() it cost k_window_run<0, true>
+// nine SGPR spills (476 -> 485); these are the texts the kernels were tuned on.
+__device__ __forceinline__ void alloc_req(const ColSrc& s, int res, int64_t pod_req, bool use_requested, int64_t& a,
+                                          int64_t& q) {
+  const DevCluster& C = s.C;
+  const uint32_t n = s.n;
   if (res < 0 || (res >= KSG_RES_EPH + 1 && pod_req == 0)) { a = 0; q = 0; return; }  // unknown / scalar not requested
   a = C.alloc[(size_t)res * C.N + n];
   if (res == KSG_RES_CPU) q = (use_requested ? C.req[n] : C.nzc[n]) + pod_req;
   else if (res == KSG_RES_MEM) q = (use_requested ? C.req[(size_t)C.N + n] : C.nzm[n]) + pod_req;
   else q = C.req[(size_t)res * C.N + n] + pod_req;
+}
+__device__ __forceinline__ void alloc_req(const RowSrc& s, int res, int64_t pod_req, bool use_requested, int64_t& a,
+                                          int64_t& q) {
+  const RowV& r = s.r;  // (a row holds resources 0..3)
+  if (res < 0 || res > 3 || (res >= KSG_RES_EPH + 1 && pod_req == 0)) { a = 0; q = 0; return; }
+  a = sel4(r.alloc, res);
+  if (res == KSG_RES_CPU) q = (use_requested ? r.req[0] : r.nzc) + pod_req;
+  else if (res == KSG_RES_MEM) q = (use_requested ? r.req[1] : r.nzm) + pod_req;
+  else q = sel4(r.req, res) + pod_req;
 }
 
 __device__ int64_t rtc_fn(const DevProfile& F, int64_t p) {
@@ -609,38 +692,130 @@ __device__ int64_t rtc_fn(const DevProfile& F, int64_t p) {
   return F.rtc_score[F.rtc_n - 1];
 }
 
-__device__ int64_t fit_score(const DevCluster& C, const DevProfile& F, const ProgView& V, uint32_t n) {
+__device__ __noinline__ int64_t rtc_fn_ool(const DevProfile& F, int64_t p) { return rtc_fn(F, p); }
+
+// NodeResourcesFit Score (resource_allocation.go score, least_allocated.go,
+// most_allocated.go, requested_to_capacity_ratio.go).  MODE 1: the compiled
+// default arguments, LeastAllocated cpu:1 memory:1: (s_cpu + s_mem) / 2.
+template <int MODE, class S, class P>
+__device__ __forceinline__ int64_t fit_score(const S& s, const DevProfile& F, const P* h) {
+  if (MODE == 1) {
+    const int64_t a0 = s.allocatable(KSG_RES_CPU), a1 = s.allocatable(KSG_RES_MEM);
+    bool ok0 = a0 != 0, ok1 = a1 != 0;
+    int64_t s0 = ok0 ? least_req_q(a0, s.nz_cpu() + h->fit_score_req[0]) : 0;
+    int64_t s1 = ok1 ? least_req_q(a1, s.nz_mem() + h->fit_score_req[1]) : 0;
+    int64_t ns = s0 + s1;
+    return ok0 && ok1 ? ns >> 1 : ns;
+  }
   int64_t ns = 0, ws = 0;
 #pragma unroll 1
   for (int i = 0; i < F.fit_n; ++i) {
     int64_t a, q;
-    alloc_req(C, n, F.fit_res[i], V.h->fit_score_req[i], false, a, q);
+    alloc_req(s, S::fit_res(F, i), h->fit_score_req[i], false, a, q);
     if (a == 0) continue;
-    int64_t s;
+    // (ColSrc reads the weight at its use: read here, k_eval<0> went 272 -> 284 SGPR spills)
+    int64_t sc, w = S::kWeightFirst ? S::fit_w(F, i) : 0;
     if (F.fit_strategy == 2) {
-      s = q > a ? rtc_fn(F, 100) : rtc_fn(F, q * 100 / a);
-      if (s <= 0) continue;
+      sc = q > a ? S::rtc(F, 100) : S::rtc(F, S::rtc_util(q, a));
+      if (sc <= 0) continue;
     } else if (F.fit_strategy == 1) {
-      s = div_small((q > a ? a : q) * 100, a);
+      sc = div_small((q > a ? a : q) * 100, a);
     } else {
-      s = q > a ? 0 : div_small((a - q) * 100, a);
+      sc = least_req(a, q);
     }
-    ns += s * F.fit_w[i];
-    ws += F.fit_w[i];
+    if (!S::kWeightFirst) w = S::fit_w(F, i);
+    ns += sc * w;
+    ws += w;
   }
   if (ws == 0) return 0;
   if (F.fit_strategy == 2) return (int64_t)round((double)ns / (double)ws);
   return div_small(ns, ws);
 }
 
-__device__ int64_t ba_score(const DevCluster& C, const DevProfile& F, const ProgView& V, uint32_t n) {
+// balancedResourceScorer's walk over op.count() operands, op(i, a, q) giving the i-th
+// (allocatable, requested): fractions in operand order, an operand without
+// allocatable skipped; two of them take the half difference, more the root of
+// the mean squared deviation, each fraction recomputed in a second pass instead
+// of keeping an array.  The order of the additions makes the result: this is its
+// statement for every kernel but ba_score_chain_cols' two (k_selftest_arith runs it
+// on the caller's pairs).
+template <class Op>
+__device__ __forceinline__ int64_t ba_walk(const Op& op) {
 #pragma clang fp contract(off)
+  int m = 0;
+  double total = 0, f0 = 0, f1 = 0, sd = 0.0;
+#pragma unroll 1
+  for (int i = 0; i < op.count(); ++i) {
+    int64_t a, q;
+    op(i, a, q);
+    if (a == 0) continue;
+    const double f = ba_frac(q, a);
+    total = total + f;
+    if (m == 0) f0 = f;
+    else if (m == 1) f1 = f;
+    m++;
+  }
+  if (m == 2) {
+    sd = ba_sd2(f0, f1);
+  } else if (m > 2) {
+    double mean = total / (double)m;
+    double sum = 0;
+#pragma unroll 1
+    for (int i = 0; i < op.count(); ++i) {
+      int64_t a, q;
+      op(i, a, q);
+      if (a == 0) continue;
+      sum = sum + ba_dev(ba_frac(q, a), mean);
+    }
+    sd = ba_sdn(sum, m);
+  }
+  return ba_final(sd);
+}
+template <class S, class P>
+struct BaOperands {  // a profile's BalancedAllocation resources on a source
+  const S& s;
+  const DevProfile& F;
+  const P* h;
+  __device__ __forceinline__ int count() const { return F.ba_n; }
+  __device__ __forceinline__ void operator()(int i, int64_t& a, int64_t& q) const {
+    alloc_req(s, S::ba_res(F, i), h->ba_req[i], true, a, q);
+  }
+};
+// NodeResourcesBalancedAllocation Score over a source.  MODE 1: cpu and memory.
+template <int MODE, class S, class P>
+__device__ __forceinline__ int64_t ba_score(const S& s, const DevProfile& F, const P* h) {
+#pragma clang fp contract(off)
+  if (MODE == 1) {
+    const int64_t a0 = s.allocatable(KSG_RES_CPU), a1 = s.allocatable(KSG_RES_MEM);
+    double sd = 0.0;
+    if (a0 != 0 && a1 != 0)
+      sd = ba_sd2(ba_frac(s.requested(KSG_RES_CPU) + h->ba_req[0], a0), ba_frac(s.requested(KSG_RES_MEM) + h->ba_req[1], a1));
+    return ba_final(sd);
+  }
+  return ba_walk(BaOperands<S, P>{s, F, h});
+}
+// the node-column kernels' calls (their pod is a program header)
+__device__ __forceinline__ uint32_t fit_filter(const DevCluster& C, const ProgView& V, uint32_t n) {
+  return fit_filter(ColSrc{C, n}, V.h, C.R);
+}
+__device__ int64_t fit_score(const DevCluster& C, const DevProfile& F, const ProgView& V, uint32_t n) {
+  return fit_score<0>(ColSrc{C, n}, F, V.h);
+}
+__device__ int64_t ba_score(const DevCluster& C, const DevProfile& F, const ProgView& V, uint32_t n) {
+  return ba_score<0>(ColSrc{C, n}, F, V.h);
+}
+// The table chain's evaluation on the node columns (k_eval<0>, k_eval_occ<0>) stays on
+// the column walk as it was: through ba_walk k_eval<0> grew its SGPR spills 272 -> 274
+// (profiles/plugin_bodies_kernel_resources.txt).  Every other kernel runs ba_walk.
+__device__ int64_t ba_score_chain_cols(const DevCluster& C, const DevProfile& F, const ProgView& V, uint32_t n) {
+#pragma clang fp contract(off)
+  const ColSrc s{C, n};
   int m = 0;
   double total = 0, f0 = 0, f1 = 0, sd = 0.0;
 #pragma unroll 1
   for (int i = 0; i < F.ba_n; ++i) {
     int64_t a, q;
-    alloc_req(C, n, F.ba_res[i], V.h->ba_req[i], true, a, q);
+    alloc_req(s, F.ba_res[i], V.h->ba_req[i], true, a, q);
     if (a == 0) continue;
     const double f = ba_frac(q, a);
     total = total + f;
@@ -656,7 +831,7 @@ __device__ int64_t ba_score(const DevCluster& C, const DevProfile& F, const Prog
 #pragma unroll 1
     for (int i = 0; i < F.ba_n; ++i) {
       int64_t a, q;
-      alloc_req(C, n, F.ba_res[i], V.h->ba_req[i], true, a, q);
+      alloc_req(s, F.ba_res[i], V.h->ba_req[i], true, a, q);
       if (a == 0) continue;
       sum = sum + ba_dev(ba_frac(q, a), mean);
     }
@@ -679,6 +854,63 @@ __device__ __forceinline__ int64_t na_score(const DevCluster& C, const ProgView&
     if (node_sel(C, V, V.sel[V.h->pref_terms_off + t], n)) s += V.i32[V.h->pref_w_off + t];
   return s;
 }
+
+// The per-node plugin switch of the kernels that walk a profile on the node
+// columns.  PM: the plugins compiled in (bit KP_*; one outside compiles to nothing).
+// PodTopologySpread and InterPodAffinity read their kernel's own state and stay
+// with the caller, which sends every other plugin here.
+__device__ __forceinline__ uint32_t filter_code(int pos, uint32_t detail) {
+  return ((uint32_t)pos << 24) | (detail & 0xFFFFFFu);
+}
+constexpr bool pm_has(uint32_t pm, int p) { return (pm >> p) & 1u; }
+// Filter of `plugin` at profile position pos on node n: KSG_FILTER_PASS or its failure code.
+template <uint32_t PM>
+__device__ __forceinline__ uint32_t node_filter(int plugin, int pos, const DevCluster& C, const ProgView& V, uint32_t n) {
+  const uint32_t flags = V.h->flags;
+  uint32_t detail = 0;
+  bool fail = false;
+  switch (plugin) {
+    case KP_FIT:
+      if constexpr (pm_has(PM, KP_FIT)) fail = (detail = fit_filter(C, V, n)) != 0;
+      break;
+    case KP_TAINT:
+      if constexpr (pm_has(PM, KP_TAINT)) {
+        const int32_t t = untolerated_taint(C, V, n);
+        if (t >= 0) { fail = true; detail = (uint32_t)t; }
+      }
+      break;
+    case KP_NA:
+      if constexpr (pm_has(PM, KP_NA)) fail = !(flags & KPF_SKIP_NA_FILTER) && !required_na(C, V, n);
+      break;
+    case KP_UNSCHED:
+      if constexpr (pm_has(PM, KP_UNSCHED)) fail = unsched_fails(C, V, n);
+      break;
+    case KP_NODENAME:
+      if constexpr (pm_has(PM, KP_NODENAME)) fail = nodename_fails(C, V, n);
+      break;
+    case KP_PORTS:
+      if constexpr (pm_has(PM, KP_PORTS)) fail = !(flags & KPF_SKIP_PORTS) && ports_fail(C, V, n);
+      break;
+    case KP_VOLUMES:
+      if constexpr (pm_has(PM, KP_VOLUMES)) fail = (detail = volume_filter(C, V, pos, n)) != 0;
+      break;
+    default: break;
+  }
+  return fail ? filter_code(pos, detail) : KSG_FILTER_PASS;
+}
+// Raw Score of `plugin` on node n (before NormalizeScore and the weight).
+template <uint32_t PM>
+__device__ __forceinline__ int64_t node_score(int plugin, const DevCluster& C, const DevProfile& F, const ProgView& V,
+                                              uint32_t n) {
+  if (pm_has(PM, KP_FIT) && plugin == KP_FIT) return fit_score(C, F, V, n);
+  if (pm_has(PM, KP_BA) && plugin == KP_BA) return ba_score(C, F, V, n);
+  if (pm_has(PM, KP_TAINT) && plugin == KP_TAINT) return taint_score(C, V, n);
+  if (pm_has(PM, KP_NA) && plugin == KP_NA) return (V.h->flags & KPF_SKIP_NA_SCORE) ? 0 : na_score(C, V, n);
+  if (pm_has(PM, KP_IMAGE) && plugin == KP_IMAGE) return image_score(C, V, n);
+  return 0;
+}
+constexpr uint32_t kPmStatic = (1u << KP_TAINT) | (1u << KP_NA);  // what a static record holds
+constexpr uint32_t kPmWhatif = kPmStatic | (1u << KP_FIT) | (1u << KP_BA);
 
 __device__ __forceinline__ bool pts_has_keys(const DevCluster& C, const ProgView& V, int c0, int c1, uint32_t n) {
   for (int c = c0; c < c1; ++c)
@@ -1072,48 +1304,21 @@ __global__ __launch_bounds__(kBlock) void k_filter_score(DevCluster C, DevProfil
     code = KSG_FILTER_PASS;
 #pragma unroll 1
     for (int pos = 0; pos < F.n; ++pos) {
-      uint32_t detail = 0;
-      bool fail = false;
       switch (F.plugins[pos]) {
-        case KP_FIT: {
-          uint32_t b = fit_filter(C, V, n);
-          if (b) { fail = true; detail = b; }
-          break;
-        }
-        case KP_TAINT: {
-          int32_t t = untolerated_taint(C, V, n);
-          if (t >= 0) { fail = true; detail = (uint32_t)t; }
-          break;
-        }
-        case KP_NA:
-          if (!(h->flags & KPF_SKIP_NA_FILTER) && !required_na(C, V, n)) fail = true;
-          break;
         case KP_PTS:
           if (!(h->flags & KPF_SKIP_PTS_FILTER)) {
             int r = pts_filter_v(C, S, V, tv, err);
-            if (r) { fail = true; detail = (uint32_t)(r - 1); }
+            if (r) code = filter_code(pos, (uint32_t)(r - 1));
           }
           break;
         case KP_IPA: {
           int r = ipa_filter_v(C, S, V, tv, ipa_flags, exist_any);
-          if (r) { fail = true; detail = (uint32_t)(r - 1); }
+          if (r) code = filter_code(pos, (uint32_t)(r - 1));
           break;
         }
-        case KP_UNSCHED: fail = unsched_fails(C, V, n); break;
-        case KP_NODENAME: fail = nodename_fails(C, V, n); break;
-        case KP_PORTS:
-          if (!(h->flags & KPF_SKIP_PORTS)) fail = ports_fail(C, V, n);
-          break;
-        case KP_VOLUMES:
-          detail = volume_filter(C, V, pos, n);
-          fail = detail != 0;
-          break;
-        default: break;
+        default: code = node_filter<~0u>(F.plugins[pos], pos, C, V, n); break;
       }
-      if (fail) {
-        code = ((uint32_t)pos << 24) | (detail & 0xFFFFFFu);
-        break;
-      }
+      if (code != KSG_FILTER_PASS) break;
     }
   }
   bool feasible = active && code == KSG_FILTER_PASS;
@@ -1132,15 +1337,8 @@ __global__ __launch_bounds__(kBlock) void k_filter_score(DevCluster C, DevProfil
     int p = F.plugins[pos];
     int64_t sc = 0;
     if (feasible) {
-      switch (p) {
-        case KP_FIT: sc = fit_score(C, F, V, n); break;
-        case KP_BA: sc = ba_score(C, F, V, n); break;
-        case KP_TAINT: sc = taint_score(C, V, n); break;
-        case KP_NA: sc = (h->flags & KPF_SKIP_NA_SCORE) ? 0 : na_score(C, V, n); break;
-        case KP_IPA: sc = ipa_score_v(C, S, tv); break;
-        case KP_IMAGE: sc = image_score(C, V, n); break;
-        default: break;
-      }
+      if (p == KP_IPA) sc = ipa_score_v(C, S, tv);
+      else sc = node_score<~0u>(p, C, F, V, n);
       O.score[(size_t)pos * C.N + n] = (int32_t)sc;
       if (sc < 0 || sc > 100) range_err = true;
       tot += sc * F.weight[pos];
@@ -1871,24 +2069,8 @@ __global__ __launch_bounds__(256) void k_whatif(DevCluster C, DevProfile F, WiAr
       }
       uint32_t code = KSG_FILTER_PASS;
 #pragma unroll 1
-      for (int pos = 0; pos < F.n && code == KSG_FILTER_PASS; ++pos) {
-        switch (F.plugins[pos]) {
-          case KP_FIT: {
-            uint32_t b = fit_filter(C, V, n);
-            if (b) code = ((uint32_t)pos << 24) | b;
-            break;
-          }
-          case KP_TAINT: {
-            int32_t t = untolerated_taint(C, V, n);
-            if (t >= 0) code = ((uint32_t)pos << 24) | ((uint32_t)t & 0xFFFFFFu);
-            break;
-          }
-          case KP_NA:
-            if (!(h->flags & KPF_SKIP_NA_FILTER) && !required_na(C, V, n)) code = (uint32_t)pos << 24;
-            break;
-          default: break;
-        }
-      }
+      for (int pos = 0; pos < F.n && code == KSG_FILTER_PASS; ++pos)
+        code = node_filter<kPmWhatif>(F.plugins[pos], pos, C, V, n);
       if (PASS == 2 && kept) A.kfilter[slot * C.N + n] = code;
       if (code != KSG_FILTER_PASS) continue;
       ++cnt;
@@ -1896,15 +2078,8 @@ __global__ __launch_bounds__(256) void k_whatif(DevCluster C, DevProfile F, WiAr
 #pragma unroll 1
       for (int pos = 0; pos < F.n; ++pos) {
         const int p = F.plugins[pos];
-        int64_t s = 0;
         if (PASS == 1 && p != KP_TAINT && p != KP_NA) continue;
-        switch (p) {
-          case KP_FIT: s = fit_score(C, F, V, n); break;
-          case KP_BA: s = ba_score(C, F, V, n); break;
-          case KP_TAINT: s = taint_score(C, V, n); break;
-          case KP_NA: s = (h->flags & KPF_SKIP_NA_SCORE) ? 0 : na_score(C, V, n); break;
-          default: break;
-        }
+        int64_t s = node_score<kPmWhatif>(p, C, F, V, n);
         if (PASS == 1) {
           mx[pos] = s > mx[pos] ? s : mx[pos];
           mn[pos] = s < mn[pos] ? s : mn[pos];
@@ -2054,7 +2229,6 @@ __global__ __launch_bounds__(256) void k_static(DevCluster C, DevProfile F, cons
     if (j >= count) break;
     const ProgView V = view(progs + prog_off[q0 + j]);
     const ksg_prog* h = V.h;
-    const bool skip_na_score = (h->flags & KPF_SKIP_NA_SCORE) != 0;
     int64_t mt = -1, ma = -1;
 #pragma unroll 1
     for (int k = 0; k < KSG_ST_NPT; ++k) {
@@ -2067,17 +2241,11 @@ __global__ __launch_bounds__(256) void k_static(DevCluster C, DevProfile F, cons
         code = KSG_FILTER_NOT_EVALUATED;
       } else {
 #pragma unroll 1
-        for (int pos = 0; pos < F.n && code == KSG_FILTER_PASS; ++pos) {
-          if (F.plugins[pos] == KP_TAINT) {
-            int32_t t = untolerated_taint(C, V, n);
-            if (t >= 0) code = ((uint32_t)pos << 24) | ((uint32_t)t & 0xFFFFFFu);
-          } else if (F.plugins[pos] == KP_NA) {
-            if (!(h->flags & KPF_SKIP_NA_FILTER) && !required_na(C, V, n)) code = (uint32_t)pos << 24;
-          }
-        }
+        for (int pos = 0; pos < F.n && code == KSG_FILTER_PASS; ++pos)
+          code = node_filter<kPmStatic>(F.plugins[pos], pos, C, V, n);
         if (code == KSG_FILTER_PASS) {
-          int64_t t = F.pos_taint >= 0 ? taint_score(C, V, n) : 0;
-          int64_t a = (F.pos_na >= 0 && !skip_na_score) ? na_score(C, V, n) : 0;
+          int64_t t = F.pos_taint >= 0 ? node_score<kPmStatic>(KP_TAINT, C, F, V, n) : 0;
+          int64_t a = F.pos_na >= 0 ? node_score<kPmStatic>(KP_NA, C, F, V, n) : 0;
           raw = ((uint32_t)t << 20) | ((uint32_t)a & KSG_RAW_NA_MASK);
           mt = t > mt ? t : mt;
           ma = a > ma ? a : ma;
@@ -2301,11 +2469,6 @@ static_assert(KSG_WIN_THREADS == 1024, "the window replay's lane maps assume 102
 #define KSG_XHDR 512       // record header: per pod feasible count, static-max achievers (Taint, NodeAffinity): 3 x KSG_BATCH ints
 #define KSG_NOT_PATCHED 0xFFFFFFFDu
 
-struct RowV {  // one node row (resource columns 0..3)
-  int64_t alloc[4], req[4];
-  int64_t nzc, nzm;
-  int32_t podcnt, allowed;
-};
 struct Pend {  // a node modified by a window: row before (base) and after it
   int32_t node, pad;  // global node index
   RowV base, after;
@@ -2436,9 +2599,9 @@ __device__ __forceinline__ StaticRec srec_at(const WinArgs& A, uint32_t q, uint3
     return StaticRec{(uint32_t)v, (uint32_t)(v >> 32)};
   }
 }
-__device__ __forceinline__ int64_t sel4(const int64_t (&v)[4], int i) {
-  return i == 0 ? v[0] : i == 1 ? v[1] : i == 2 ? v[2] : v[3];
-}
+// The row kernels' Fit filter stays on its hand-unrolled form: through fit_filter
+// over RowSrc, k_chain_run<2, kPmTab, 8, 4, 256> grew its SGPR spills 709 -> 724
+// and cfg4 ran 1.3% slower (profiles/plugin_bodies_kernel_resources.txt).
 template <class P>
 __device__ __forceinline__ uint32_t fit_filter_row(const RowV& r, const P* h, uint32_t R) {
   uint32_t bits = 0;
@@ -2457,105 +2620,14 @@ __device__ __forceinline__ uint32_t fit_filter_row(const RowV& r, const P* h, ui
   }
   return bits;
 }
-__device__ __forceinline__ void alloc_req_row(const RowV& r, int res, int64_t pod_req, bool use_requested, int64_t& a,
-                                              int64_t& q) {
-  if (res < 0 || res > 3 || (res >= KSG_RES_EPH + 1 && pod_req == 0)) { a = 0; q = 0; return; }
-  a = sel4(r.alloc, res);
-  if (res == KSG_RES_CPU) q = (use_requested ? r.req[0] : r.nzc) + pod_req;
-  else if (res == KSG_RES_MEM) q = (use_requested ? r.req[1] : r.nzm) + pod_req;
-  else q = sel4(r.req, res) + pod_req;
-}
-__device__ __noinline__ int64_t rtc_fn_ool(const DevProfile& F, int64_t p) { return rtc_fn(F, p); }
-__device__ __forceinline__ int64_t least_req(int64_t a, int64_t q) {  // leastRequestedScore
-  return q > a ? 0 : div_small((a - q) * 100, a);
-}
-// leastRequestedScore for the compiled default arguments: floor((a-q)*100/a)
-// from one f64 reciprocal estimate (relative error near 2^-28, quotient <= 100,
-// so the truncated estimate is the quotient or one beside it) and one exact
-// integer correction, branch-free.  Exact wherever x = (a-q)*100 fits int64
-// (0 <= q, a < 2^56): the conversions of x and a round by 2^-53, far inside the
-// estimate's own error, d <= 101 keeps d*a in int64, and the remainder is an
-// integer difference.  (A 2^52 gate to the 64-bit divide stood here; no operand
-// told the two apart, so it went.)
-__device__ __forceinline__ int64_t least_req_q(int64_t a, int64_t q) {
-  if (q > a || a <= 0) return 0;
-  int64_t x = (a - q) * 100;
-  int64_t d = (int64_t)((double)x * __builtin_amdgcn_rcp((double)a));
-  int64_t rem = x - d * a;
-  return rem >= a ? d + 1 : (rem < 0 ? d - 1 : d);
-}
+// the row kernels' calls of the score bodies (RowSrc)
 template <int MODE, class P>
 __device__ __forceinline__ int64_t fit_score_row(const RowV& r, const DevProfile& F, const P* h) {
-  if (MODE == 1) {  // LeastAllocated, cpu:1 memory:1 (the defaults): (s_cpu + s_mem) / 2
-    bool ok0 = r.alloc[0] != 0, ok1 = r.alloc[1] != 0;
-    int64_t s0 = ok0 ? least_req_q(r.alloc[0], r.nzc + h->fit_score_req[0]) : 0;
-    int64_t s1 = ok1 ? least_req_q(r.alloc[1], r.nzm + h->fit_score_req[1]) : 0;
-    int64_t ns = s0 + s1;
-    return ok0 && ok1 ? ns >> 1 : ns;
-  }
-  int64_t ns = 0, ws = 0;
-#pragma unroll 1
-  for (int i = 0; i < F.fit_n; ++i) {
-    int64_t a, q;
-    alloc_req_row(r, F.fit_res_d[i], h->fit_score_req[i], false, a, q);
-    if (a == 0) continue;
-    int64_t s, w = F.fit_w_d[i];
-    if (F.fit_strategy == 2) {
-      s = q > a ? rtc_fn_ool(F, 100) : rtc_fn_ool(F, div_small(q * 100, a));
-      if (s <= 0) continue;
-    } else if (F.fit_strategy == 1) {
-      s = div_small((q > a ? a : q) * 100, a);
-    } else {
-      s = least_req(a, q);
-    }
-    ns += s * w;
-    ws += w;
-  }
-  if (ws == 0) return 0;
-  if (F.fit_strategy == 2) return (int64_t)round((double)ns / (double)ws);
-  return div_small(ns, ws);
+  return fit_score<MODE>(RowSrc{r}, F, h);
 }
-// balancedResourceScorer: fractions in resource order; the >2-resource case
-// recomputes each fraction in a second pass instead of keeping an array.
 template <int MODE, class P>
 __device__ __forceinline__ int64_t ba_score_row(const RowV& r, const DevProfile& F, const P* h) {
-#pragma clang fp contract(off)
-  double sd = 0.0;
-  if (MODE == 1) {
-    bool ok0 = r.alloc[0] != 0, ok1 = r.alloc[1] != 0;
-    if (ok0 && ok1) {
-      sd = ba_sd2(ba_frac(r.req[0] + h->ba_req[0], r.alloc[0]), ba_frac(r.req[1] + h->ba_req[1], r.alloc[1]));
-    }
-    return ba_final(sd);
-  }
-  int m = 0;
-  double total = 0, f0 = 0, f1 = 0;
-#pragma unroll 1
-  for (int i = 0; i < F.ba_n; ++i) {
-    int64_t a, q;
-    alloc_req_row(r, F.ba_res_d[i], h->ba_req[i], true, a, q);
-    if (a == 0) continue;
-    const double f = ba_frac(q, a);
-    total = total + f;
-    if (m == 0) f0 = f;
-    else if (m == 1) f1 = f;
-    m++;
-  }
-  if (m == 2) {
-    sd = ba_sd2(f0, f1);
-  } else if (m > 2) {
-    double mean = total / (double)m;
-    double sum = 0;
-#pragma unroll 1
-    for (int i = 0; i < F.ba_n; ++i) {
-      int64_t a, q;
-      alloc_req_row(r, F.ba_res_d[i], h->ba_req[i], true, a, q);
-      if (a == 0) continue;
-      sum = sum + ba_dev(ba_frac(q, a), mean);
-    }
-    sd = ba_sdn(sum, m);
-  }
-  return ba_final(sd);
+  return ba_score<MODE>(RowSrc{r}, F, h);
 }
 
 // Evaluate one (pod, node row) for a Fit/BA profile: filter code, raw Fit and BA, total.
@@ -2735,9 +2807,18 @@ __global__ void k_selftest_lanes(const uint64_t* in, int32_t* bad) {
 // Self-test of the arithmetic fast paths (diagnostic ABI, ksg_debug_arith): the
 // engine's own __device__ functions applied element-wise to the caller's
 // operands, column c of element i at in[c * n + i]; doubles as bit patterns.
-__device__ __forceinline__ int64_t least_req_q(int64_t a, int64_t q);
 __device__ __forceinline__ int32_t least_req_d(double ad, double ra, double x);
 __device__ __forceinline__ int64_t d2bits(double v) { return (int64_t)__double_as_longlong(v); }
+// KSG_ARITH_BA's operand source for ba_walk: element i's (requested, allocatable) column pairs
+struct PairSrc {
+  const int64_t* in;
+  uint32_t n, i, cols;
+  __device__ __forceinline__ int count() const { return (int)(cols / 2); }
+  __device__ __forceinline__ void operator()(int c, int64_t& a, int64_t& q) const {
+    q = in[(size_t)(2 * c) * n + i];
+    a = in[(size_t)(2 * c + 1) * n + i];
+  }
+};
 __global__ __launch_bounds__(256) void k_selftest_arith(int op, const int64_t* __restrict__ in, uint32_t cols,
                                                         int64_t* __restrict__ out, uint32_t n) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -2760,34 +2841,7 @@ __global__ __launch_bounds__(256) void k_selftest_arith(int op, const int64_t* _
       r = d2bits(wc_frac((double)x, ad, ra));
       break;
     }
-    case KSG_ARITH_BA: {  // cols / 2 (requested, allocatable) pairs, as ba_score / ba_score_row walk them
-      const int k = (int)(cols / 2);
-      int m = 0;
-      double total = 0, f0 = 0, f1 = 0, sd = 0.0;
-      for (int c = 0; c < k; ++c) {
-        const int64_t q = in[(size_t)(2 * c) * n + i], a = in[(size_t)(2 * c + 1) * n + i];
-        if (a == 0) continue;
-        const double f = ba_frac(q, a);
-        total = total + f;
-        if (m == 0) f0 = f;
-        else if (m == 1) f1 = f;
-        m++;
-      }
-      if (m == 2) {
-        sd = ba_sd2(f0, f1);
-      } else if (m > 2) {
-        const double mean = total / (double)m;
-        double sum = 0;
-        for (int c = 0; c < k; ++c) {
-          const int64_t q = in[(size_t)(2 * c) * n + i], a = in[(size_t)(2 * c + 1) * n + i];
-          if (a == 0) continue;
-          sum = sum + ba_dev(ba_frac(q, a), mean);
-        }
-        sd = ba_sdn(sum, m);
-      }
-      r = ba_final(sd);
-      break;
-    }
+    case KSG_ARITH_BA: r = ba_walk(PairSrc{in, n, i, cols}); break;
     case KSG_ARITH_GO_LOG: r = d2bits(go_log(__longlong_as_double(x))); break;
     case KSG_ARITH_IPA_NORM: r = ipa_norm(x, y, z); break;
     default: break;

@@ -947,7 +947,7 @@ __device__ __forceinline__ void eval_body(DevCluster& C, const DevProfile& F, co
           break;
         case KP_BA:
           if constexpr (PMH(KP_BA))
-            sc = (RUN && ROWM) ? ba_s : ROWM == 2 ? ba_score_row<1>(row, F, h) : ROWM == 1 ? ba_score_row<0>(row, F, h) : ba_score(C, F, V, n);
+            sc = (RUN && ROWM) ? ba_s : ROWM == 2 ? ba_score_row<1>(row, F, h) : ROWM == 1 ? ba_score_row<0>(row, F, h) : ba_score_chain_cols(C, F, V, n);
           break;
         case KP_TAINT:
           if constexpr (PMH(KP_TAINT)) sc = taint_score(C, V, n);

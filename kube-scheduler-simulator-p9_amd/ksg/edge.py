@@ -135,6 +135,54 @@ def gen_fit(variant, n_nodes=60, n_pods=160, seed=None):
     return {"profile": prof, "nodes": nodes, "pods": [], "queue": queue}
 
 
+FPGA = "example.com/fpga"
+FIVE_STRATEGIES = ("least", "most", "rtc")
+
+
+def five_seed(strategy: str) -> int:
+    return 20250131 * 100 + 90 + FIVE_STRATEGIES.index(strategy)
+
+
+def gen_fit5(strategy, n_nodes=70, n_pods=12, seed=None):
+    """The ``fit_most`` / ``fit_rtc`` cluster shape with a second scalar resource:
+    five resource columns, which the row kernels (four resources a row) do not
+    hold, so every path scores on the node columns.  LeastAllocated and
+    MostAllocated over all five with unequal weights, RequestedToCapacityRatio
+    over cpu / memory / both scalars; BalancedAllocation over all five.  Kept out
+    of EDGE_VARIANTS, so that the edge seeds and parametrisations stay put."""
+    seed = five_seed(strategy) if seed is None else seed
+    r = Rng(seed)
+    nodes, queue = _fit_cluster(r, n_nodes, n_pods)
+    for n in nodes:
+        if r.pct() < 60:
+            v = str(r.pick([0, 2, 4]))
+            n["status"]["allocatable"][FPGA] = v
+            n["status"]["capacity"][FPGA] = v
+    for j, p in enumerate(queue):
+        res = p["spec"]["containers"][0].setdefault("resources", {}).setdefault("requests", {})
+        if j % 3 == 0:
+            res[FPGA] = str(1 + r.below(2))
+        if j % 4 == 1:  # neither scalar: both are skipped by the scorers
+            for c in p["spec"]["containers"]:
+                c.get("resources", {}).get("requests", {}).pop(GPU, None)
+            res.pop(FPGA, None)
+    prof = make_profile([("NodeResourcesFit", 1), ("NodeResourcesBalancedAllocation", 1)], seed)
+    pc = prof["pluginConfig"]
+    five = [{"name": "cpu", "weight": 1}, {"name": "memory", "weight": 2}, {"name": EPH, "weight": 1},
+            {"name": GPU, "weight": 3}, {"name": FPGA, "weight": 2}]
+    if strategy == "rtc":
+        pc["NodeResourcesFit"] = {"scoringStrategy": {"type": "RequestedToCapacityRatio", "resources": [
+            {"name": "cpu", "weight": 2}, {"name": "memory", "weight": 1}, {"name": GPU, "weight": 1},
+            {"name": FPGA, "weight": 3}],
+            "requestedToCapacityRatio": {"shape": [{"utilization": 0, "score": 0}, {"utilization": 40, "score": 8},
+                                                   {"utilization": 100, "score": 3}]}}}
+    else:
+        kind = {"least": "LeastAllocated", "most": "MostAllocated"}[strategy]
+        pc["NodeResourcesFit"] = {"scoringStrategy": {"type": kind, "resources": five}}
+    pc["NodeResourcesBalancedAllocation"] = {"resources": [{"name": n["name"], "weight": 1} for n in five]}
+    return {"profile": prof, "nodes": nodes, "pods": [], "queue": queue}
+
+
 NA_TAINTS = [{"key": "dedicated", "value": "infra", "effect": "NoSchedule"},
              {"key": "dedicated", "value": "gpu", "effect": "NoExecute"},
              {"key": "spot", "value": "", "effect": "PreferNoSchedule"},
