@@ -1988,7 +1988,6 @@ __global__ __launch_bounds__(256) void k_toggle_groups(DevCluster C, const uint6
   }
 }
 
-
 // ----------------------------------------------------------------- what-if batches (cfg5)
 // A step of `count` queue pods is scheduled against ONE frozen snapshot (no
 // assume between them), then all placements are bound together
@@ -2195,7 +2194,6 @@ __global__ void k_whatif_merge(const ksg_pod_summary* recv, uint32_t ranks, uint
   }
   sums[j] = m;
 }
-
 
 // ----------------------------------------------------------------- static pre-pass (per-pod chain, Taint/NA profiles)
 // TaintToleration's and NodeAffinity's Filter and raw Score of a (pod, node)
@@ -2491,7 +2489,6 @@ __device__ __forceinline__ RowV* rec_rows(uint8_t* rec) { return reinterpret_cas
 __device__ __forceinline__ const RowV* rec_rows(const uint8_t* rec) {
   return reinterpret_cast<const RowV*>(rec + KSG_XHDR + kRecKeys * 8);
 }
-
 
 struct PodLite {  // the fields of ksg_prog the Fit/BA evaluation reads (LDS-staged)
   int64_t req[4];
@@ -3279,7 +3276,7 @@ constexpr int kWcNpt = 4;  // nodes per thread (1 and 2 were measured slower and
 // every requirement on every node of the thread (no per-term loops, no ballots,
 // no pointer chasing through the program) and folds the outcomes into a
 // failed-term mask: bit 0 the node selector, bits 1..15 the required terms,
-// bits 16..22 the preferred terms.  Host-checked per pod (prog_need bit 19):
+// bits 16..22 the preferred terms.  Host-checked per pod (prog_need, need::kDecodable):
 // flattened requirements, <= 15 required terms, <= KSG_WC_MAXREQ requirements.
 #define KSG_WC_MAXREQ 24
 #define KSG_WC_PREF_BIT 16
@@ -3309,7 +3306,7 @@ struct WcPod {
 };
 static_assert(sizeof(WcReq) == 32 && sizeof(WcPod) == 160 + 32 * KSG_WC_MAXREQ, "WcPod layout");
 
-// Is program h a class-path pod the decoder can flatten (prog_need bit 19)?
+// Is program h a class-path pod the decoder can flatten (prog_need, need::kDecodable)?
 __host__ __device__ inline bool wc_decodable(const ksg_prog* h) {
   if (!(h->flags & KPF_FLAT_NA) || h->n_req_terms > 15 || h->n_pref_terms > 7) return false;
   const ksg_sel* sel = reinterpret_cast<const ksg_sel*>(reinterpret_cast<const uint8_t*>(h) + h->off_sel);
@@ -5295,7 +5292,6 @@ __global__ __launch_bounds__(KSG_WIN_THREADS) void k_window_run(DevCluster C, De
   }
 }
 
-
 template <class T>
 struct DBuf {
   T* p = nullptr;
@@ -5495,8 +5491,6 @@ struct Engine::Impl {
   DBuf<int64_t> cpm, cpm2;
   DBuf<EvalTotals> cetot;
   int run_on = 1;         // persistent segments (k_chain_run): KSG_RUN=0 turns them off
-  int run_bt = 256;       // k_chain_run threads per block (KSG_RUN_BT=256|512)
-  uint32_t run_cap512 = 0;
   uint32_t run_cap = 0;   // blocks every one of which is resident at once (k_chain_run), 0: not queried yet
   uint32_t run_min = 2;   // shortest segment launched persistently (KSG_RUN_MIN)
   DBuf<RunSync> rsync;    // k_chain_run's flag / handshake (zeroed per launch) and sticky abort word
@@ -5526,7 +5520,6 @@ struct Engine::Impl {
   size_t vp_k = 0;
   ViewDev vp_V{};
   uint8_t* vp_hout = nullptr;
-  int run_overlap = 0;           // k_chain_run: pod k+1's class-table reads during pod k's hand-offs (KSG_RUN_OVERLAP=1; measured no faster)
   int run_defer = 1;             // k_chain_run: the owner's independent node-level assume deferred (KSG_RUN_DEFER=0: off)
   uint64_t win_runs = 0, win_fallbacks = 0;  // diagnostic: persistent window launches / not co-resident
   uint32_t fold_blocks = 256;  // table chain: k_fold above this many blocks (KSG_FOLD_BLOCKS; tests force it)
@@ -5572,7 +5565,7 @@ struct Engine::Impl {
   DBuf<uint32_t> bfilter;
   DBuf<int32_t> bscore, btotal;
   std::vector<size_t> prog_off;
-  std::vector<uint32_t> prog_need;  // bit0 pts, bit1 ipa
+  std::vector<uint32_t> prog_need;  // per program: the paths it may take (namespace need, prog_need_of)
   bool has_pts = false, has_ipa = false;
   bool force_per_pod = false;
   int eval_mode = 0;  // 1: default Fit/BA arguments (compiled specialisation)
@@ -5671,6 +5664,15 @@ static bool stream_sync(Engine::Impl& I, hipStream_t s, std::string& err) {
   return true;
 }
 
+// An option of the environment as a number; false (and *out untouched) when it is not set.
+// (Every option goes through strtol, also those once read by strtoul / strtoull: the same
+// value after the casts for anything up to LONG_MAX.)
+static bool env_long(const char* name, long* out) {
+  const char* e = std::getenv(name);
+  if (e) *out = std::strtol(e, nullptr, 10);
+  return e != nullptr;
+}
+
 Engine::Engine() : p_(new Impl()) {}
 Engine::~Engine() {
   if (p_->comm) (void)ncclCommDestroy(p_->comm);
@@ -5698,32 +5700,37 @@ Engine::~Engine() {
 bool Engine::init(const EngineConfig& cfg, std::string& err) {
   Impl& I = *p_;
   I.cfg = cfg;
-  if (const char* e = std::getenv("KSG_FOLD_BLOCKS")) I.fold_blocks = (uint32_t)std::strtoul(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_RANK_TILE")) {  // the largest power of two <= the value, within [128, kRankTile]
-    const unsigned long v = std::strtoul(e, nullptr, 10);
+  // the KSG_* options (DESIGN.md "Runtime and build options that remain"), read once per context
+  long v = 0;
+  if (env_long("KSG_FOLD_BLOCKS", &v)) I.fold_blocks = (uint32_t)v;
+  if (env_long("KSG_RANK_TILE", &v)) {  // the largest power of two <= the value, within [128, kRankTile]
     I.rank_tile = 128;
-    while (I.rank_tile < kRankTile && 2ul * I.rank_tile <= v) I.rank_tile *= 2;
+    while (I.rank_tile < kRankTile && 2ul * I.rank_tile <= (unsigned long)v) I.rank_tile *= 2;
   }
-  if (const char* e = std::getenv("KSG_RUN")) I.run_on = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_RUN_BT")) I.run_bt = std::strtol(e, nullptr, 10) == 512 ? 512 : 256;
-  if (const char* e = std::getenv("KSG_RUN_MIN")) I.run_min = std::max<uint32_t>(1, (uint32_t)std::strtoul(e, nullptr, 10));
-  if (const char* e = std::getenv("KSG_RUN_LAG")) I.run_lag = std::min<uint32_t>(4096, (uint32_t)std::strtoul(e, nullptr, 10));
-  if (const char* e = std::getenv("KSG_RUN_NORES")) I.run_need_extra = std::strtol(e, nullptr, 10) != 0 ? 1u : 0u;
-  if (const char* e = std::getenv("KSG_WIN_RUN")) I.win_run_on = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_WIN_REPLAY2")) I.win_replay2 = I.win_replay2_stat = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_RUN_OVERLAP")) I.run_overlap = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_RUN_DEFER")) I.run_defer = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_VIEW_COPY")) I.view_copy = (int)std::strtol(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_RUN_SPIN")) I.run_spin = std::max<uint32_t>(1, (uint32_t)std::strtoul(e, nullptr, 10));
-  if (const char* e = std::getenv("KSG_RUN_WAIT_US"))
-    I.run_wait_us = std::max<uint32_t>(10, std::min<uint32_t>(1000000, (uint32_t)std::strtoul(e, nullptr, 10)));
-  if (const char* e = std::getenv("KSG_WHATIF_REC_MB")) I.wi_rec_mb = (size_t)std::strtoull(e, nullptr, 10);
-  if (const char* e = std::getenv("KSG_WHATIF_CLASSES")) I.wi_classes = std::strtol(e, nullptr, 10) != 0;
+  if (env_long("KSG_RUN", &v)) I.run_on = (int)v;
+  if (env_long("KSG_RUN_MIN", &v)) I.run_min = std::max<uint32_t>(1, (uint32_t)v);
+  if (env_long("KSG_RUN_LAG", &v)) I.run_lag = std::min<uint32_t>(4096, (uint32_t)v);
+  if (env_long("KSG_RUN_NORES", &v)) I.run_need_extra = v != 0 ? 1u : 0u;
+  if (env_long("KSG_WIN_RUN", &v)) I.win_run_on = (int)v;
+  if (env_long("KSG_WIN_REPLAY2", &v)) I.win_replay2 = I.win_replay2_stat = (int)v;
+  if (env_long("KSG_RUN_DEFER", &v)) I.run_defer = (int)v;
+  if (env_long("KSG_VIEW_COPY", &v)) I.view_copy = (int)v;
+  if (env_long("KSG_VIEW_FUSE", &v)) I.view_fuse = (int)v;
+  if (env_long("KSG_RUN_SPIN", &v)) I.run_spin = std::max<uint32_t>(1, (uint32_t)v);
+  if (env_long("KSG_RUN_WAIT_US", &v)) I.run_wait_us = std::max<uint32_t>(10, std::min<uint32_t>(1000000, (uint32_t)v));
+  if (env_long("KSG_WHATIF_REC_MB", &v)) I.wi_rec_mb = (size_t)v;
+  if (env_long("KSG_WHATIF_CLASSES", &v)) I.wi_classes = v != 0;
   I.wi_wide = std::getenv("KSG_WHATIF_WIDE") != nullptr;
-  if (const char* e = std::getenv("KSG_OCC_BLOCKS")) {
-    I.occ_blocks = (uint32_t)std::strtoul(e, nullptr, 10);
+  if (env_long("KSG_OCC_BLOCKS", &v)) {
+    I.occ_blocks = (uint32_t)v;
     I.occ_force = I.occ_blocks == 0;
   }
+  if (env_long("KSG_STATIC_DEC", &v)) I.static_dec = (int)v;
+  if (env_long("KSG_STATIC_RUN_MB", &v)) I.static_run_mb = (uint32_t)v;
+  if (env_long("KSG_STATIC_OVERLAP", &v)) I.static_overlap = (int)v;
+  if (env_long("KSG_STATIC_BESIDE_TEST", &v)) I.static_beside_test = (int)v;
+  if (env_long("KSG_STATIC_CHUNK", &v))  // diagnostic (tests): smaller static chunks
+    I.stat_chunk_cap = v > 0 ? (uint32_t)std::max<long>(KSG_BATCH, v / KSG_BATCH * KSG_BATCH) : 0;
   HIPCHK(hipSetDevice(cfg.device));
   if (cfg.stream) {
     I.stream = (hipStream_t)cfg.stream;
@@ -5740,11 +5747,6 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
     HIPCHK(hipStreamCreateWithPriority(&I.sstream, hipStreamNonBlocking, least));
-    if (const char* e = std::getenv("KSG_STATIC_DEC")) I.static_dec = (int)std::strtol(e, nullptr, 10);
-    if (const char* e = std::getenv("KSG_STATIC_RUN_MB")) I.static_run_mb = (uint32_t)std::strtoul(e, nullptr, 10);
-    if (const char* e = std::getenv("KSG_STATIC_OVERLAP")) I.static_overlap = (int)std::strtol(e, nullptr, 10);
-    if (const char* e = std::getenv("KSG_STATIC_BESIDE_TEST")) I.static_beside_test = (int)std::strtol(e, nullptr, 10);
-    if (const char* e = std::getenv("KSG_VIEW_FUSE")) I.view_fuse = (int)std::strtol(e, nullptr, 10);
   }
   HIPCHK(hipEventCreate(&I.ev0));
   HIPCHK(hipEventCreate(&I.ev1));
@@ -5796,10 +5798,6 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
   for (int i = 0; i < F.n; ++i)
     I.batch_ok &= (F.plugins[i] == KP_FIT || F.plugins[i] == KP_BA || F.plugins[i] == KP_TAINT || F.plugins[i] == KP_NA);
   I.batch_static = I.batch_ok && I.static_ok;
-  if (const char* e = std::getenv("KSG_STATIC_CHUNK")) {  // diagnostic (tests): smaller static chunks
-    long v = std::strtol(e, nullptr, 10);
-    I.stat_chunk_cap = v > 0 ? (uint32_t)std::max<long>(KSG_BATCH, v / KSG_BATCH * KSG_BATCH) : 0;
-  }
   return true;
 }
 
@@ -6016,6 +6014,87 @@ static uint32_t eval_tiles(uint32_t N, uint32_t cus) {
   return std::max<uint32_t>((N + KSG_TILE * npt - 1) / (KSG_TILE * npt), 1);
 }
 
+// Impl::prog_need: one word per program, the paths its pod may take.  prog_need_of
+// computes it (replace_program, set_programs and note_program store it); the
+// host paths ask through the predicates below.
+namespace need {
+enum : uint32_t {
+  kPts = 1u << 0,         // PodTopologySpread constraints
+  kIpa = 1u << 1,         // InterPodAffinity: always set (existing pods' terms may apply to any pod)
+  kTable = 1u << 2,       // the table chain
+  kPtsRaw = 1u << 3,      // ... with its PodTopologySpread raw-score pass (k_ptsraw)
+  kPrefShift = 8,         // bits 8..15: preferred NodeAffinity terms of the what-if class path
+  kPrefRecord = 0xFFu,    // ... or this: a negative weight or more than 7 terms — the record path
+  kSmallReq = 1u << 16,   // cpu / memory requests in [0, 2^44) (the class path's doubles stay exact)
+  kSegment = 1u << 17,    // nothing but the node row and the class tables changes on its assume (no host
+                          // ports, volume claims or CSI volumes): a persistent segment may hold it
+  kSmallClass = 1u << 18, // the persistent chain's small size class (kRunLK lookups, kRunTS constraints)
+  kDecodable = 1u << 19,  // the class path's decoder flattens its NodeAffinity (wc_decodable)
+};
+static bool pts(uint32_t nd) { return (nd & kPts) != 0; }
+static bool table(uint32_t nd) { return (nd & kTable) != 0; }
+static bool pts_raw(uint32_t nd) { return (nd & kPtsRaw) != 0; }
+static bool segment(uint32_t nd) { return (nd & kSegment) != 0; }
+static bool small_class(uint32_t nd) { return (nd & kSmallClass) != 0; }
+static bool small_req(uint32_t nd) { return (nd & kSmallReq) != 0; }
+static bool decodable(uint32_t nd) { return (nd & kDecodable) != 0; }
+static uint32_t pref_terms(uint32_t nd) { return (nd >> kPrefShift) & 0xFFu; }  // (kPrefRecord: none counted)
+}  // namespace need
+static uint32_t prog_need_of(const ksg_prog* h) {
+  uint32_t nd = need::kIpa;
+  if (h->n_tsc_filter + h->n_tsc_score > 0) nd |= need::kPts;
+  if (h->tab & KTAB_ON) nd |= need::kTable;
+  if (h->tab & KTAB_PTS_MULTI) nd |= need::kPtsRaw;
+  if (h->n_port_own == 0 && h->n_pvc == 0 && h->n_csi == 0) nd |= need::kSegment;
+  if (h->n_lk <= kRunLK && h->n_tsc_filter + h->n_tsc_score <= kRunTS) nd |= need::kSmallClass;
+  const int32_t* i32 = reinterpret_cast<const int32_t*>(reinterpret_cast<const uint8_t*>(h) + h->off_i32);
+  uint32_t np = h->n_pref_terms > 7 ? need::kPrefRecord : (uint32_t)h->n_pref_terms;
+  for (int t = 0; t < h->n_pref_terms && np != need::kPrefRecord; ++t)
+    if (i32[h->pref_w_off + t] < 0) np = need::kPrefRecord;
+  bool small = true;
+  for (int c = 0; c < 2; ++c)
+    for (int64_t v : {h->req[c], h->fit_score_req[c], h->ba_req[c]}) small &= v >= 0 && v < ((int64_t)1 << 44);
+  if (small) nd |= need::kSmallReq;
+  if (wc_decodable(h)) nd |= need::kDecodable;
+  return nd | np << need::kPrefShift;
+}
+
+// Sampled kernel timing (Engine::sample_kernel, kernel_time): a run brackets
+// some of its launches with a pair of I.sev events.  Which launches is each
+// site's own `gate`; a launch is sampled when sampling is on, its gate holds
+// and a pair is left.
+static bool ensure_sample_events(Engine::Impl& I, size_t n_events, std::string& err) {
+  while (I.sample_every && I.sev.size() < n_events) {
+    hipEvent_t e;
+    HIPCHK(hipEventCreate(&e));
+    I.sev.push_back(e);
+  }
+  return true;
+}
+static bool every_nth(const Engine::Impl& I, uint32_t j) { return I.sample_every && (j % I.sample_every) == 0; }
+static bool sample_begin(Engine::Impl& I, hipStream_t s, bool gate, bool& sampled, std::string& err) {
+  sampled = I.sample_every && gate && I.n_samples * 2 + 2 <= I.sev.size();
+  if (sampled) HIPCHK(hipEventRecord(I.sev[I.n_samples * 2], s));
+  return true;
+}
+static bool sample_end(Engine::Impl& I, hipStream_t s, bool sampled, std::string& err) {
+  if (sampled) {
+    HIPCHK(hipEventRecord(I.sev[I.n_samples * 2 + 1], s));
+    I.n_samples++;
+  }
+  return true;
+}
+
+// Per-pair outputs of the kept range of pods go to their own slices.
+static bool kept_pod(const Engine::Impl& I, uint32_t j) { return I.keep_n && j >= I.keep_first && j < I.keep_first + I.keep_n; }
+static void kept_outputs(const Engine::Impl& I, uint32_t j, DevOut& O) {
+  if (!kept_pod(I, j)) return;
+  const size_t k = j - I.keep_first, N = I.N;
+  O.filter = I.kfilter.p + k * N;
+  O.score = I.kscore.p + k * N * KSG_MAX_PLUGINS;
+  O.total = I.ktotal.p + k * N;
+}
+
 // The handshake verdict of the persistent launch just queued (k_chain_run,
 // k_window_run): the host waits for it (the work queued before runs first).
 // 1 go, 2 not co-resident (its blocks left untouched), 3 an earlier launch of the
@@ -6036,6 +6115,19 @@ static bool tables_ready(Engine::Impl& I, std::string& err);
 // ordered by those waits: window j's tile lists, send buffer, output-ring slots
 // and P-list slot are those of window j-2, whose replay it waited for (and that
 // replay waited for j-2's exchange).
+// The window kernels [static records][default Fit/BA arguments], and their dynamic LDS size set once.
+static void (*const kWindow[2][2])(DevCluster, DevProfile, WinArgs) = {{k_window<0, false>, k_window<1, false>},
+                                                                       {k_window<0, true>, k_window<1, true>}};
+static void (*const kWindowRun[2][2])(DevCluster, DevProfile, WinArgs, WinRunArgs, RunSync*, WinSync*, RunCtl) = {
+    {k_window_run<0>, k_window_run<1>}, {k_window_run<0, true>, k_window_run<1, true>}};
+static bool window_lds_attr(std::string& err) {
+  static bool done = false;
+  for (int i = 0; i < 4 && !done; ++i)
+    for (const void* f : {(const void*)kWindow[i / 2][i % 2], (const void*)kWindowRun[i / 2][i % 2]})
+      HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WinLDS)));
+  done = true;
+  return true;
+}
 static bool run_batches_split(Engine::Impl& I, const WinArgs& A0, uint32_t first, uint32_t count, uint32_t T,
                               std::string& err) {
   hipStream_t s = I.stream;
@@ -6055,8 +6147,7 @@ static bool run_batches_split(Engine::Impl& I, const WinArgs& A0, uint32_t first
   const size_t tt_sz = (size_t)KSG_BATCH * T * KSG_TOPK, tf_sz = (size_t)KSG_BATCH * T * 3;
   const dim3 blk(KSG_WIN_THREADS);
   auto launch = [&](hipStream_t st, const WinArgs& a, uint32_t blocks) {
-    if (I.eval_mode == 1) hipLaunchKernelGGL((k_window<1, false>), dim3(blocks), blk, sizeof(WinLDS), st, C, I.F, a);
-    else hipLaunchKernelGGL((k_window<0, false>), dim3(blocks), blk, sizeof(WinLDS), st, C, I.F, a);
+    hipLaunchKernelGGL(kWindow[0][I.eval_mode == 1], dim3(blocks), blk, sizeof(WinLDS), st, C, I.F, a);
   };
   for (int64_t j = 0; j <= (int64_t)nwin; ++j) {
     if (j < (int64_t)nwin) {  // evaluation of window E = j, exchange, merge (engine stream)
@@ -6073,13 +6164,10 @@ static bool run_batches_split(Engine::Impl& I, const WinArgs& A0, uint32_t first
       a.pprev = I.pend.p + (size_t)(P & 1) * KSG_BATCH;
       a.pprev_n = I.pend_n.p + (P & 1);
       if (E >= 2) HIPCHK(hipStreamWaitEvent(s, I.xr[E & 1], 0));  // the replay of E-2
-      const bool sampled = I.sample_every && I.n_samples * 2 + 2 <= I.sev.size();
-      if (sampled) HIPCHK(hipEventRecord(I.sev[I.n_samples * 2], s));
+      bool sampled;
+      if (!sample_begin(I, s, true, sampled, err)) return false;
       launch(s, a, 1 + a.ne * T);
-      if (sampled) {
-        HIPCHK(hipEventRecord(I.sev[I.n_samples * 2 + 1], s));
-        I.n_samples++;
-      }
+      if (!sample_end(I, s, sampled, err)) return false;
       HIPCHK(hipEventRecord(I.xe[E & 1], s));
       HIPCHK(hipStreamWaitEvent(sx, I.xe[E & 1], 0));
       if (!xgather(I, kXchgBytes, err, a.erec, sx)) return false;
@@ -6124,24 +6212,11 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
   // beside the replay block in one round (one 1,024-thread block per CU)
   const uint32_t T = eval_tiles(I.N, I.n_cus), npt = eval_npt(I.N, I.n_cus), tile_len = npt * KSG_TILE;
   const uint32_t nwin = (count + KSG_BATCH - 1) / KSG_BATCH;
-  if (I.sample_every) {
-    size_t need = 2 * (nwin + 2);
-    while (I.sev.size() < need) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      I.sev.push_back(e);
-    }
-  }
+  if (!ensure_sample_events(I, 2 * ((size_t)nwin + 2), err)) return false;
   I.n_samples = 0;
   I.n_st = 0;
   I.stat_pods_sampled = 0;
-  static bool attr = false;
-  if (!attr) {
-    const void* fns[4] = {(const void*)k_window<0, false>, (const void*)k_window<1, false>,
-                          (const void*)k_window<0, true>, (const void*)k_window<1, true>};
-    for (const void* f : fns) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WinLDS)));
-    attr = true;
-  }
+  if (!window_lds_attr(err)) return false;
   HIPCHK(hipEventRecord(I.ev0, s));
   HIPCHK(hipMemsetAsync(I.pend_n.p, 0, 2 * sizeof(int32_t), s));
   WinArgs A{};
@@ -6237,7 +6312,7 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
   // nodes' taints fit the id set (KSG_STATIC_DEC=0: the program-walking k_static)
   auto static_dec_ok = [&](uint32_t q0, uint32_t cn) {
     bool dec = I.static_dec && I.max_taints <= 4 && I.max_tid < 64 && !I.taint_dup;
-    for (uint32_t q = q0; dec && q < q0 + cn; ++q) dec = (I.prog_need[q] & (1u << 19)) != 0;
+    for (uint32_t q = q0; dec && q < q0 + cn; ++q) dec = need::decodable(I.prog_need[q]);
     return dec;
   };
   // ready: k_static_dec beside the persistent loop, counting its pod groups there
@@ -6336,14 +6411,6 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
       HIPCHK(hipHostMalloc((void**)&I.hverdict, kVerdictBytes, hipHostMallocCoherent | hipHostMallocMapped));
       HIPCHK(hipMemsetAsync(I.rsync.p, 0, sizeof(RunSync), s));  // (the sticky abort word starts clear)
     }
-    static bool wattr = false;
-    if (!wattr) {
-      HIPCHK(hipFuncSetAttribute((const void*)k_window_run<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WinLDS)));
-      HIPCHK(hipFuncSetAttribute((const void*)k_window_run<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WinLDS)));
-      HIPCHK(hipFuncSetAttribute((const void*)k_window_run<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WinLDS)));
-      HIPCHK(hipFuncSetAttribute((const void*)k_window_run<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WinLDS)));
-      wattr = true;
-    }
     HIPCHK(hipMemsetAsync(I.wsync.p, 0, sizeof(WinSync), s));
     HIPCHK(hipMemsetAsync(I.rsync.p, 0, kRunSyncReset, s));
     HIPCHK(hipMemsetAsync(I.arrive.p, 0, 2 * KSG_BATCH * 32 * sizeof(uint32_t), s));
@@ -6372,22 +6439,11 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
       RC.side_arrive = I.sready.p + sgroups;
       RC.side_need = side_blocks;
     }
-    const bool sampled = I.sample_every && I.n_samples * 2 + 2 <= I.sev.size();
-    if (sampled) HIPCHK(hipEventRecord(I.sev[I.n_samples * 2], s));
-    if (stat_run) {
-      if (I.eval_mode == 1)
-        hipLaunchKernelGGL((k_window_run<1, true>), dim3(grid), dim3(KSG_WIN_THREADS), sizeof(WinLDS), s, C, I.F, AP, R, I.rsync.p, I.wsync.p, RC);
-      else
-        hipLaunchKernelGGL((k_window_run<0, true>), dim3(grid), dim3(KSG_WIN_THREADS), sizeof(WinLDS), s, C, I.F, AP, R, I.rsync.p, I.wsync.p, RC);
-    } else if (I.eval_mode == 1) {
-      hipLaunchKernelGGL(k_window_run<1>, dim3(grid), dim3(KSG_WIN_THREADS), sizeof(WinLDS), s, C, I.F, AP, R, I.rsync.p, I.wsync.p, RC);
-    } else {
-      hipLaunchKernelGGL(k_window_run<0>, dim3(grid), dim3(KSG_WIN_THREADS), sizeof(WinLDS), s, C, I.F, AP, R, I.rsync.p, I.wsync.p, RC);
-    }
-    if (sampled) {
-      HIPCHK(hipEventRecord(I.sev[I.n_samples * 2 + 1], s));
-      I.n_samples++;
-    }
+    bool sampled;
+    if (!sample_begin(I, s, true, sampled, err)) return false;
+    hipLaunchKernelGGL(kWindowRun[stat_run][I.eval_mode == 1], dim3(grid), dim3(KSG_WIN_THREADS), sizeof(WinLDS), s, C, I.F, AP, R,
+                       I.rsync.p, I.wsync.p, RC);
+    if (!sample_end(I, s, sampled, err)) return false;
     HIPCHK(hipGetLastError());
     if (overlap && I.static_beside_test == 1 && !issue_side()) return false;  // (tests: launched after the loop)
     I.run_used = true;
@@ -6413,7 +6469,7 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
       return true;
     }
     I.win_fallbacks++;  // v == 2: its blocks left untouched; the per-window launches
-    if (sampled) I.n_samples--;
+    if (sampled) I.n_samples--;  // (the launch that left is not a sample)
     // (the side kernel's records and maxima are rewritten by the per-window loop's
     // k_static: it waits for the side kernel first)
     if (overlap) HIPCHK(hipStreamWaitEvent(s, I.sev_ready, 0));
@@ -6445,21 +6501,12 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
     const bool chunk_start = stat && A.ne && (A.e0 - first) % chunk == 0;
     const uint32_t cidx = chunk_start ? (A.e0 - first) / chunk : 0;
     if (chunk_start && !issue_static(cidx, s)) return false;
-    bool sampled = I.sample_every && A.ne && A.nw && I.n_samples * 2 + 2 <= I.sev.size();
-    if (sampled) HIPCHK(hipEventRecord(I.sev[I.n_samples * 2], s));
+    bool sampled;
+    if (!sample_begin(I, s, A.ne && A.nw, sampled, err)) return false;
     dim3 grid(1 + A.ne * T);
     const dim3 blk(KSG_WIN_THREADS);
-    if (stat) {
-      if (I.eval_mode == 1) hipLaunchKernelGGL((k_window<1, true>), grid, blk, sizeof(WinLDS), s, C, I.F, A);
-      else hipLaunchKernelGGL((k_window<0, true>), grid, blk, sizeof(WinLDS), s, C, I.F, A);
-    } else {
-      if (I.eval_mode == 1) hipLaunchKernelGGL((k_window<1, false>), grid, blk, sizeof(WinLDS), s, C, I.F, A);
-      else hipLaunchKernelGGL((k_window<0, false>), grid, blk, sizeof(WinLDS), s, C, I.F, A);
-    }
-    if (sampled) {
-      HIPCHK(hipEventRecord(I.sev[I.n_samples * 2 + 1], s));
-      I.n_samples++;
-    }
+    hipLaunchKernelGGL(kWindow[stat][I.eval_mode == 1], grid, blk, sizeof(WinLDS), s, C, I.F, A);
+    if (!sample_end(I, s, sampled, err)) return false;
     if (sharded && A.ne) {
       if (!xgather(I, kXchgBytes, err)) return false;
       hipLaunchKernelGGL(k_window_gmerge, dim3(A.ne), dim3(64), 0, s, I.xrecv.p, I.xranks, I.xrows.p, A.pprev,
@@ -6501,35 +6548,79 @@ static PodLite pod_lite(const std::vector<uint8_t>& prog) {
   return q;
 }
 
-// run_queue's per-pod decisions: bit0 PodTopologySpread constraints, bit1
-// InterPodAffinity (existing pods' terms may apply to any pod), bit2 the table
-// chain, bit3 its PodTopologySpread raw-score pass.
-static uint32_t prog_need_of(const ksg_prog* h) {
-  uint32_t need = 2;
-  if (h->n_tsc_filter + h->n_tsc_score > 0) need |= 1;
-  if (h->tab & KTAB_ON) need |= 4;
-  if (h->tab & KTAB_PTS_MULTI) need |= 8;
-  // bit 17: nothing but the node row and the class tables changes on its assume
-  // (no host ports, volume claims or CSI volumes): a persistent segment may hold it
-  if (h->n_port_own == 0 && h->n_pvc == 0 && h->n_csi == 0) need |= 1u << 17;
-  // bit 18: the persistent chain's small size class (kRunLK lookups, kRunTS constraints)
-  if (h->n_lk <= kRunLK && h->n_tsc_filter + h->n_tsc_score <= kRunTS) need |= 1u << 18;
-  // bits 8..15: preferred NodeAffinity terms of the what-if class path (0xFF: a
-  // negative weight or more than 7 terms — the record path)
-  const int32_t* i32 = reinterpret_cast<const int32_t*>(reinterpret_cast<const uint8_t*>(h) + h->off_i32);
-  uint32_t np = h->n_pref_terms > 7 ? 0xFFu : (uint32_t)h->n_pref_terms;
-  for (int t = 0; t < h->n_pref_terms && np != 0xFFu; ++t)
-    if (i32[h->pref_w_off + t] < 0) np = 0xFFu;
-  // bit 16: cpu / memory requests in [0, 2^44) (the class path's doubles stay exact)
-  bool small = true;
-  for (int c = 0; c < 2; ++c)
-    for (int64_t v : {h->req[c], h->fit_score_req[c], h->ba_req[c]}) small &= v >= 0 && v < ((int64_t)1 << 44);
-  // bit 19: the class path's decoder flattens its NodeAffinity (wc_decodable)
-  if (wc_decodable(h)) need |= 1u << 19;
-  return need | np << 8 | (small ? 1u << 16 : 0u);
-}
-
 static bool exchange(Engine::Impl& I, const void* src, size_t bytes, std::string& err);
+
+// A what-if step's choice of path and its chunk of pods: the class path
+// (k_whatif_cls1/2), pass-1 records (k_whatif_rec1/2, 4- or 8-byte) or both
+// passes recomputing every pair (k_whatif<1>, <2>); sets A's record widths.
+struct WhatifPlan {
+  bool use_cls = false, use_rec = false, narrow = false;
+  uint32_t chunk = 0, tiles = 1;
+};
+static bool whatif_plan(Engine::Impl& I, uint32_t first, uint32_t count, WiArgs& A, WhatifPlan& P, std::string& err) {
+  // Pass 1 leaves an 8-byte record per (pod, node) — feasibility, the Fit/BA
+  // weighted sum, the raw Taint / NodeAffinity scores — so that pass 2 only
+  // normalises and picks (the snapshot is frozen for the step).  Pods go in
+  // chunks whose records fit KSG_WHATIF_REC_MB (default 40 GiB of the 288 GB;
+  // 0: pass 2 recomputes every pair).
+  const uint32_t N = std::max<uint32_t>(I.N, 1);
+  const size_t rec_mb = I.wi_rec_mb;
+  int64_t wsum = 0, wall = 0;  // positive weights: Fit + BalancedAllocation, every plugin
+  bool wts_ok = true;
+  for (int i = 0; i < I.F.n; ++i) {
+    wall += I.F.weight[i] > 0 ? I.F.weight[i] : 0;
+    if (I.F.plugins[i] != KP_FIT && I.F.plugins[i] != KP_BA) continue;
+    wsum += I.F.weight[i] > 0 ? I.F.weight[i] : 0;
+    wts_ok &= I.F.weight[i] >= 0;
+  }
+  A.need_eph = I.any_eph_req ? 1u : 0u;
+  // the class path (k_whatif_cls1/2): nothing per pair in memory; KSG_WHATIF_CLASSES=0 off
+  // (the class key holds the Fit/BA sum in 24 bits: 100 x the weights below 2^24, none negative)
+  P.use_cls = I.eval_mode == 1 && !I.any_eph_req && I.R <= 4 && I.static_fits && I.max_taints <= 4 &&
+              I.max_tid < 64 && !I.taint_dup && I.cols_small && rec_mb > 0 && wts_ok &&
+              100 * wsum < ((int64_t)1 << 24);
+  P.use_cls &= I.wi_classes;
+  for (uint32_t q = first; P.use_cls && q < first + count; ++q) {
+    const uint32_t nd = I.prog_need[q], np = need::pref_terms(nd);  // (0..7 terms, or kPrefRecord)
+    P.use_cls = np != need::kPrefRecord && ((I.max_taints + 1) << np) <= KSG_WC_CLS && need::small_req(nd) &&
+                need::decodable(nd);
+  }
+  P.use_rec = !P.use_cls && rec_mb > 0 && I.R <= 4 && I.static_fits && 100 * wsum < (int64_t)1 << 30;
+  // record fields as narrow as the cluster allows: 4-byte records when the raw
+  // NodeAffinity (<= the programs' largest weight sum), raw Taint (<= most taints
+  // on a node) and Fit/BA sum (<= 100 x their weights) fit 30 bits
+  auto bits = [](uint64_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b; };
+  A.bw_a = bits((uint64_t)I.max_na_sum);
+  A.bw_t = bits(I.max_taints);
+  A.bw_tot = bits((uint64_t)(100 * wsum));
+  A.small = 100 * wall < ((int64_t)1 << 31) && !I.wi_wide ? 1u : 0u;  // (WIDE: 64-bit path too)
+  P.narrow = A.bw_a + A.bw_t + A.bw_tot <= 30 && !I.wi_wide;
+  if (!P.narrow) { A.bw_a = 20; A.bw_t = 12; A.bw_tot = 30; }
+  const size_t rbytes = P.narrow ? 4 : 8;
+  P.chunk = count;
+  if (P.use_rec) {
+    const size_t per_pod = (size_t)N * rbytes;
+    const size_t fit = (rec_mb << 20) / per_pod / KSG_WI_PODS * KSG_WI_PODS;
+    P.chunk = (uint32_t)std::min<size_t>(count, std::max<size_t>(fit, KSG_WI_PODS));
+    std::string aerr;  // no room: smaller chunks
+    while (!I.wrec_pairs.alloc(((size_t)P.chunk * N * rbytes + 7) / 8, aerr) && P.chunk > KSG_WI_PODS) {
+      (void)hipGetLastError();  // (the failed hipMalloc's error is not the run's)
+      P.chunk = std::max<uint32_t>(P.chunk / 2 / KSG_WI_PODS * KSG_WI_PODS, KSG_WI_PODS);
+    }
+    if (((size_t)P.chunk * N * rbytes + 7) / 8 > I.wrec_pairs.n) { err = aerr; return false; }
+  }
+  P.tiles = std::max<uint32_t>((I.N + KSG_WC_TILE - 1) / KSG_WC_TILE, 1);
+  // class path scratch per pod: tiles x (class row + count), folded row + flag
+  const size_t wc_words = (size_t)P.tiles * KSG_WC_CLS + ((size_t)P.tiles + 1) / 2 + KSG_WC_CLS + 1;
+  if (P.use_cls) {
+    const size_t fit = (rec_mb << 20) / (wc_words * 8) / KSG_WC_PODS * KSG_WC_PODS;
+    P.chunk = (uint32_t)std::min<size_t>(count, std::max<size_t>(fit, KSG_WC_PODS));
+    if (!I.wrec_pairs.alloc((size_t)P.chunk * wc_words, err) ||
+        !I.wc_pods.alloc((size_t)P.chunk * (sizeof(WcPod) / 8), err))
+      return false;
+  }
+  return true;
+}
 
 bool Engine::run_whatif(uint32_t first, uint32_t count, std::string& err) {
   Impl& I = *p_;
@@ -6563,86 +6654,22 @@ bool Engine::run_whatif(uint32_t first, uint32_t count, std::string& err) {
   A.kfilter = I.kfilter.p;
   A.kscore = I.kscore.p;
   A.ktotal = I.ktotal.p;
-  if (I.sample_every) {
-    while (I.sev.size() < 4) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      I.sev.push_back(e);
-    }
-  }
+  if (!ensure_sample_events(I, 4, err)) return false;  // (a pair per pass)
   I.n_samples = 0;
   HIPCHK(hipEventRecord(I.ev0, s));
   if (count) {
-    // Pass 1 leaves an 8-byte record per (pod, node) — feasibility, the Fit/BA
-    // weighted sum, the raw Taint / NodeAffinity scores — so that pass 2 only
-    // normalises and picks (the snapshot is frozen for the step).  Pods go in
-    // chunks whose records fit KSG_WHATIF_REC_MB (default 40 GiB of the 288 GB;
-    // 0: pass 2 recomputes every pair).
-    const uint32_t N = std::max<uint32_t>(I.N, 1);
-    const size_t rec_mb = I.wi_rec_mb;
-    int64_t wsum = 0;
-    for (int i = 0; i < I.F.n; ++i)
-      if (I.F.plugins[i] == KP_FIT || I.F.plugins[i] == KP_BA) wsum += I.F.weight[i] > 0 ? I.F.weight[i] : 0;
-    A.need_eph = I.any_eph_req ? 1u : 0u;
-    // the class path (k_whatif_cls1/2): nothing per pair in memory; KSG_WHATIF_CLASSES=0 off
-    // (the class key holds the Fit/BA sum in 24 bits: 100 x the weights below 2^24, none negative)
-    bool wts_ok = true;
-    for (int i = 0; i < I.F.n; ++i)
-      if (I.F.plugins[i] == KP_FIT || I.F.plugins[i] == KP_BA) wts_ok &= I.F.weight[i] >= 0;
-    bool use_cls = I.eval_mode == 1 && !I.any_eph_req && I.R <= 4 && I.static_fits && I.max_taints <= 4 &&
-                   I.max_tid < 64 && !I.taint_dup && I.cols_small && rec_mb > 0 && wts_ok &&
-                   100 * wsum < ((int64_t)1 << 24);
-    use_cls &= I.wi_classes;
-    for (uint32_t q = first; use_cls && q < first + count; ++q) {
-      const uint32_t np = (I.prog_need[q] >> 8) & 0xFFu;
-      use_cls = np <= 7 && ((I.max_taints + 1) << np) <= KSG_WC_CLS && (I.prog_need[q] & (1u << 16)) &&
-                (I.prog_need[q] & (1u << 19));
-    }
-    const bool use_rec = !use_cls && rec_mb > 0 && I.R <= 4 && I.static_fits && 100 * wsum < (int64_t)1 << 30;
-    // record fields as narrow as the cluster allows: 4-byte records when the raw
-    // NodeAffinity (<= the programs' largest weight sum), raw Taint (<= most taints
-    // on a node) and Fit/BA sum (<= 100 x their weights) fit 30 bits
-    auto bits = [](uint64_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b; };
-    A.bw_a = bits((uint64_t)I.max_na_sum);
-    A.bw_t = bits(I.max_taints);
-    A.bw_tot = bits((uint64_t)(100 * wsum));
-    {
-      int64_t wall = 0;
-      for (int i = 0; i < I.F.n; ++i) wall += I.F.weight[i] > 0 ? I.F.weight[i] : 0;
-      A.small = 100 * wall < ((int64_t)1 << 31) && !I.wi_wide ? 1u : 0u;  // (WIDE: 64-bit path too)
-    }
-    const bool narrow = A.bw_a + A.bw_t + A.bw_tot <= 30 && !I.wi_wide;
-    if (!narrow) { A.bw_a = 20; A.bw_t = 12; A.bw_tot = 30; }
-    const size_t rbytes = narrow ? 4 : 8;
-    uint32_t chunk = count;
-    if (use_rec) {
-      const size_t per_pod = (size_t)N * rbytes;
-      const size_t fit = (rec_mb << 20) / per_pod / KSG_WI_PODS * KSG_WI_PODS;
-      chunk = (uint32_t)std::min<size_t>(count, std::max<size_t>(fit, KSG_WI_PODS));
-      std::string aerr;  // no room: smaller chunks
-      while (!I.wrec_pairs.alloc(((size_t)chunk * N * rbytes + 7) / 8, aerr) && chunk > KSG_WI_PODS) {
-        (void)hipGetLastError();  // (the failed hipMalloc's error is not the run's)
-        chunk = std::max<uint32_t>(chunk / 2 / KSG_WI_PODS * KSG_WI_PODS, KSG_WI_PODS);
-      }
-      if (((size_t)chunk * N * rbytes + 7) / 8 > I.wrec_pairs.n) { err = aerr; return false; }
-    }
-    const uint32_t tiles = std::max<uint32_t>((I.N + KSG_WC_TILE - 1) / KSG_WC_TILE, 1);
-    // class path scratch per pod: tiles x (class row + count), folded row + flag
-    const size_t wc_words = (size_t)tiles * KSG_WC_CLS + ((size_t)tiles + 1) / 2 + KSG_WC_CLS + 1;
-    if (use_cls) {
-      const size_t fit = (rec_mb << 20) / (wc_words * 8) / KSG_WC_PODS * KSG_WC_PODS;
-      chunk = (uint32_t)std::min<size_t>(count, std::max<size_t>(fit, KSG_WC_PODS));
-      if (!I.wrec_pairs.alloc((size_t)chunk * wc_words, err) ||
-          !I.wc_pods.alloc((size_t)chunk * (sizeof(WcPod) / 8), err))
-        return false;
-    }
+    WhatifPlan P;
+    if (!whatif_plan(I, first, count, A, P, err)) return false;
+    void (*const rec1)(DevCluster, DevProfile, WiArgs, const uint8_t*, const uint64_t*) =
+        I.eval_mode == 1 ? (P.narrow ? k_whatif_rec1<uint32_t, 1> : k_whatif_rec1<uint64_t, 1>)
+                         : (P.narrow ? k_whatif_rec1<uint32_t, 0> : k_whatif_rec1<uint64_t, 0>);
     const dim3 pods((count + 255) / 256);
     hipLaunchKernelGGL(k_init_summaries, pods, dim3(256), 0, s, I.sums.p + first, count, I.F);
-    for (uint32_t c0 = 0; c0 < count; c0 += chunk) {
+    for (uint32_t c0 = 0; c0 < count; c0 += P.chunk) {
       WiArgs a = A;
       a.q0 = first + c0;
-      a.count = std::min(chunk, count - c0);
-      a.rec = use_rec ? (void*)I.wrec_pairs.p : nullptr;
+      a.count = std::min(P.chunk, count - c0);
+      a.rec = P.use_rec ? (void*)I.wrec_pairs.p : nullptr;
       const dim3 grid(std::max<uint32_t>((I.N + 256 * KSG_WI_NPT - 1) / (256 * KSG_WI_NPT), 1),
                       (a.count + KSG_WI_PODS - 1) / KSG_WI_PODS);
       const dim3 grid1((a.count + KSG_WI_PODS - 1) / KSG_WI_PODS, std::max<uint32_t>((I.N + 255) / 256, 1));
@@ -6650,45 +6677,34 @@ bool Engine::run_whatif(uint32_t first, uint32_t count, std::string& err) {
                        (a.count + KSG_WI_PODS - 1) / KSG_WI_PODS);
       const dim3 cpods((a.count + 255) / 256);
       const size_t xb = (size_t)a.count * sizeof(ksg_pod_summary);
-      if (use_cls) {
+      if (P.use_cls) {
         a.wc_part = I.wrec_pairs.p;
-        a.wc_cls = a.wc_part + (size_t)a.count * tiles * KSG_WC_CLS;
+        a.wc_cls = a.wc_part + (size_t)a.count * P.tiles * KSG_WC_CLS;
         a.wc_cnt = reinterpret_cast<uint32_t*>(a.wc_cls + (size_t)a.count * KSG_WC_CLS);
-        a.wc_flag = a.wc_cnt + (size_t)a.count * tiles;
+        a.wc_flag = a.wc_cnt + (size_t)a.count * P.tiles;
       }
-      const dim3 gridc((a.count + KSG_WC_PODS - 1) / KSG_WC_PODS, tiles);
+      const dim3 gridc((a.count + KSG_WC_PODS - 1) / KSG_WC_PODS, P.tiles);
       for (int pass = 1; pass <= 2; ++pass) {
-        const bool sampled = I.sample_every != 0 && c0 == 0;
-        if (sampled) HIPCHK(hipEventRecord(I.sev[2 * (pass - 1)], s));
+        bool sampled;  // (the first chunk's passes: pass p in pair p - 1)
+        if (!sample_begin(I, s, c0 == 0, sampled, err)) return false;
         const bool kept_here = I.keep_n && I.keep_first < a.q0 + a.count && I.keep_first + I.keep_n > a.q0;
-        if (pass == 1 && use_cls) {
+        if (pass == 1 && P.use_cls) {
           I.path_pods[3]++;
           WcPod* wp = reinterpret_cast<WcPod*>(I.wc_pods.p);
           hipLaunchKernelGGL(k_wc_decode, dim3((a.count + 63) / 64), dim3(64), 0, s, C, I.F, a, wp);
           hipLaunchKernelGGL(k_whatif_cls1<kWcNpt>, gridc, dim3(256), 0, s, C, I.F, a, wp);
-          hipLaunchKernelGGL(k_whatif_cls2, dim3(a.count), dim3(KSG_WC_CLS), 0, s, I.F, a, tiles, I.xranks > 1 ? 1 : 0);
-        } else if (pass == 2 && use_cls) {
-          if (I.xranks > 1) hipLaunchKernelGGL(k_whatif_cls2, dim3(a.count), dim3(KSG_WC_CLS), 0, s, I.F, a, tiles, 2);
+          hipLaunchKernelGGL(k_whatif_cls2, dim3(a.count), dim3(KSG_WC_CLS), 0, s, I.F, a, P.tiles, I.xranks > 1 ? 1 : 0);
+        } else if (pass == 2 && P.use_cls) {
+          if (I.xranks > 1) hipLaunchKernelGGL(k_whatif_cls2, dim3(a.count), dim3(KSG_WC_CLS), 0, s, I.F, a, P.tiles, 2);
           if (kept_here) hipLaunchKernelGGL(k_whatif<2>, grid, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
-        } else if (pass == 1 && use_rec) {
-          if (I.eval_mode == 1) {
-            if (narrow) hipLaunchKernelGGL((k_whatif_rec1<uint32_t, 1>), grid1, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
-            else hipLaunchKernelGGL((k_whatif_rec1<uint64_t, 1>), grid1, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
-          } else {
-            if (narrow) hipLaunchKernelGGL((k_whatif_rec1<uint32_t, 0>), grid1, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
-            else hipLaunchKernelGGL((k_whatif_rec1<uint64_t, 0>), grid1, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
-          }
-        }
-        else if (pass == 1) hipLaunchKernelGGL(k_whatif<1>, grid, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
-        else if (use_rec) {
-          if (narrow) hipLaunchKernelGGL(k_whatif_rec2<uint32_t>, grid2, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
-          else hipLaunchKernelGGL(k_whatif_rec2<uint64_t>, grid2, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
+        } else if (pass == 1 && P.use_rec) {
+          hipLaunchKernelGGL(rec1, grid1, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
+        } else if (pass == 1) hipLaunchKernelGGL(k_whatif<1>, grid, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
+        else if (P.use_rec) {
+          hipLaunchKernelGGL(P.narrow ? k_whatif_rec2<uint32_t> : k_whatif_rec2<uint64_t>, grid2, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
           if (kept_here) hipLaunchKernelGGL(k_whatif<2>, grid, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
         } else hipLaunchKernelGGL(k_whatif<2>, grid, dim3(256), 0, s, C, I.F, a, a.progs, a.prog_off);
-        if (sampled) {
-          HIPCHK(hipEventRecord(I.sev[2 * (pass - 1) + 1], s));
-          I.n_samples++;
-        }
+        if (!sample_end(I, s, sampled, err)) return false;
         if (I.xranks > 1) {  // per-pod partials of every shard -> global values on every rank
           if (!exchange(I, I.sums.p + a.q0, xb, err)) return false;
           hipLaunchKernelGGL(k_whatif_merge, cpods, dim3(256), 0, s,
@@ -6697,9 +6713,9 @@ bool Engine::run_whatif(uint32_t first, uint32_t count, std::string& err) {
         }
       }
     }
-    I.wi_chunk = chunk;
-    I.wi_rec = use_rec;
-    I.wi_cls = use_cls;
+    I.wi_chunk = P.chunk;
+    I.wi_rec = P.use_rec;
+    I.wi_cls = P.use_cls;
     hipLaunchKernelGGL(k_whatif_select, pods, dim3(256), 0, s, A);
     hipLaunchKernelGGL(k_whatif_bind, pods, dim3(256), 0, s, C, A);
   }
@@ -7516,7 +7532,7 @@ bool Engine::replace_program(uint32_t q, const std::vector<uint8_t>& prog, std::
 
 bool Engine::normalized(uint32_t j, std::vector<int32_t>& norm, std::string& err) {
   Impl& I = *p_;
-  if (!(I.keep_n && j >= I.keep_first && j < I.keep_first + I.keep_n)) { err = "outputs not kept for this pod"; return false; }
+  if (!kept_pod(I, j)) { err = "outputs not kept for this pod"; return false; }
   const size_t N = I.N, k = j - I.keep_first;
   if (!I.knorm.alloc(std::max<size_t>(N, 1) * KSG_MAX_PLUGINS, err)) return false;
   DevCluster C = I.cluster();
@@ -7583,7 +7599,7 @@ bool Engine::view(uint32_t j, const ViewCfg& cfg, const ViewLayout& lay, uint8_t
 bool Engine::view_impl(uint32_t j, const ViewCfg& cfg, const ViewLayout& lay, uint8_t* host, std::string& err, bool wait,
                        bool arm) {
   Impl& I = *p_;
-  if (!(I.keep_n && j >= I.keep_first && j < I.keep_first + I.keep_n)) { err = "outputs not kept for this pod"; return false; }
+  if (!kept_pod(I, j)) { err = "outputs not kept for this pod"; return false; }
   if (lay.N != I.N || lay.n_raw != (uint32_t)I.F.n) { err = "view layout of another snapshot"; return false; }
   if (lay.bytes > I.vblk.n || !I.vblk.p) I.vblk_fresh = true;
   if (!I.vblk.alloc(lay.bytes, err)) return false;
@@ -7752,78 +7768,108 @@ bool Engine::keep_outputs(uint32_t keep_first, uint32_t keep_n, std::string& err
 
 static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::string& err);
 
-bool Engine::run_queue(uint32_t first, uint32_t count, bool commit, std::string& err) {
-  Impl& I = *p_;
-  if (first + count > I.prog_off.size()) { err = "program index out of range"; return false; }
-  if (!tables_ready(I, err)) return false;
-  if (commit && batch_path()) return run_batches(I, first, count, err);
+// ---- A queue run outside the window path (Engine::run_queue): the static
+// chain for Taint / NodeAffinity profiles; otherwise per pod a persistent
+// segment, a table-chain cycle or a scanning-chain cycle.
+
+// The state of one run_queue call that its paths share.
+struct QueueRun {
+  uint32_t first, count;
+  bool commit;
+  hipStream_t s;
+  DevCluster C;
+  DevScratch S;
+  bool xchain;          // sharded per-pod chain (exchange points X1..X4)
+  int pts_pos;          // PodTopologySpread's position in the profile, or -1
+  int rowm;             // the table chain's eval_row specialisation
+  uint32_t pmask;       // the profile's device plugins (kernel specialisations)
+  ChainArgs CA;         // table chain (table_chain.hip): pod index on the device, partials per block
+  bool pending = false; // logged assumes whose existing-pod table rows are not written yet
+  bool run_ok = false;  // persistent segments may run
+  XLay XL;
+  int64_t* xs = nullptr;         // the exchange buffers (sharded)
+  const int64_t* xrv = nullptr;
+};
+
+// The k_chain_run instantiations, most specialised first: a segment launches
+// the first whose row mode equals the run's, whose plugin set covers the
+// profile's and whose size class holds the segment's pods; run_cap is the
+// fewest co-resident blocks over all of them.
+typedef void (*ChainRunFn)(DevCluster, DevProfile, ChainArgs, uint32_t, RunSync*, uint64_t*, uint64_t*, RunCtl,
+                           const uint8_t*, const uint64_t*);
+struct ChainRunVariant {
+  int rowm;
+  uint32_t pmask;
+  bool small_class;
+  ChainRunFn fn;
+};
+static const ChainRunVariant kChainRun[] = {
+    {2, kPmTab, true, k_chain_run<2, kPmTab, kRunLK, kRunTS>},
+    {2, kPmTab, false, k_chain_run<2, kPmTab>},
+    {2, kPmTabTN, false, k_chain_run<2, kPmTabTN>},
+    {2, ~0u, false, k_chain_run<2, ~0u>},
+    {1, ~0u, false, k_chain_run<1, ~0u>},
+};
+// Blocks every one of which is resident at once, whichever variant runs (0: none can run).
+static bool chain_run_cap(const Engine::Impl& I, uint32_t& cap, std::string& err) {
+  int occ = 1 << 30;
+  for (const ChainRunVariant& v : kChainRun) {
+    int o = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, v.fn, kChain, 0));
+    occ = std::min(occ, o);
+  }
+  // (MI355X_MICROARCH.md: the hardware may admit one block per CU fewer than the query)
+  cap = occ <= 0 ? 0u : I.n_cus * (uint32_t)(occ >= 2 ? occ - 1 : occ);
+  return true;
+}
+
+// rows of the logged pods [log_base, j); the log restarts at `next` (a pod of the
+// scanning chain is not logged: the log restarts after it)
+static void queue_flush(QueueRun& Q, uint32_t j, uint32_t next) {
+  if (Q.pending) hipLaunchKernelGGL(k_flush_appends, dim3(1), dim3(kBlock), 0, Q.s, Q.C, Q.CA, j - Q.CA.log_base);
+  Q.pending = false;
+  Q.CA.log_base = next;
+}
+
+// The static chain: k_static over a chunk of pods, then one k_fs_static per pod.
+static bool queue_static_chain(Engine::Impl& I, uint32_t first, uint32_t count, bool commit, std::string& err) {
   hipStream_t s = I.stream;
   DevCluster C = I.cluster();
-  DevScratch S = I.scratch();
+  const uint32_t N = I.N;
+  const dim3 gN((N + kBlock - 1) / kBlock), b(kBlock);
+  const size_t Nn = std::max<uint32_t>(N, 1);
+  const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(count, ((size_t)64 << 20) / (Nn * sizeof(StaticRec))));
+  if (!I.stat.alloc((size_t)chunk * Nn, err) || !I.mpred.alloc(2 * (size_t)chunk, err)) return false;
+  for (uint32_t c0 = first; c0 < first + count; c0 += chunk) {
+    const uint32_t cn = std::min(chunk, first + count - c0);
+    HIPCHK(hipMemsetAsync(I.mpred.p, 0xFF, 2 * (size_t)cn * sizeof(int64_t), s));  // -1: no statically feasible node
+    const dim3 grid(std::max<uint32_t>((N + 256 * KSG_ST_NPT - 1) / (256 * KSG_ST_NPT), 1),
+                    (cn + KSG_ST_PODS - 1) / KSG_ST_PODS);
+    hipLaunchKernelGGL(k_static, grid, dim3(256), 0, s, C, I.F, I.progs.p, I.prog_off_d.p, c0, cn, I.stat.p, I.mpred.p, 0);
+    for (uint32_t j = c0; j < c0 + cn; ++j) {
+      DevOut O{I.filter.p, I.score.p, I.total.p, I.sums.p + j, nullptr, commit ? 1 : 0, I.prow.p + j};
+      kept_outputs(I, j, O);
+      bool sampled;
+      if (!sample_begin(I, s, every_nth(I, j), sampled, err)) return false;
+      hipLaunchKernelGGL(k_fs_static, gN, b, 0, s, C, I.F, O, I.progs.p + I.prog_off[j], I.stat.p + (size_t)(j - c0) * Nn,
+                         I.mpred.p + 2 * (size_t)(j - c0), I.saux.p);
+      if (!sample_end(I, s, sampled, err)) return false;
+    }
+  }
+  return true;
+}
+
+// What the per-pod paths share: the table chain's arguments, the exchange
+// buffers of a sharded run, the segments' cap and their handshake words.
+static bool queue_setup(Engine::Impl& I, QueueRun& Q, std::string& err) {
   const DevProfile& F = I.F;
-  uint32_t N = I.N;
-  dim3 gN((N + kBlock - 1) / kBlock), b(kBlock);
-  int pts_pos = -1;
+  hipStream_t s = Q.s;
+  Q.pts_pos = -1;
   for (int i = 0; i < F.n; ++i)
-    if (F.plugins[i] == KP_PTS) pts_pos = i;
-  if (I.sample_every) {
-    size_t need = 2 * ((count + I.sample_every - 1) / I.sample_every + 1);
-    while (I.sev.size() < need) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      I.sev.push_back(e);
-    }
-  }
-  I.n_samples = 0;
-  HIPCHK(hipEventRecord(I.ev0, s));
-  const bool xchain = I.xranks > 1;  // sharded per-pod chain (exchange points X1..X4)
-  if (I.static_ok && I.static_fits && !xchain) {
-    const size_t Nn = std::max<uint32_t>(N, 1);
-    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(count, ((size_t)64 << 20) / (Nn * sizeof(StaticRec))));
-    if (!I.stat.alloc((size_t)chunk * Nn, err) || !I.mpred.alloc(2 * (size_t)chunk, err)) return false;
-    for (uint32_t c0 = first; c0 < first + count; c0 += chunk) {
-      const uint32_t cn = std::min(chunk, first + count - c0);
-      HIPCHK(hipMemsetAsync(I.mpred.p, 0xFF, 2 * (size_t)cn * sizeof(int64_t), s));  // -1: no statically feasible node
-      const dim3 grid(std::max<uint32_t>((N + 256 * KSG_ST_NPT - 1) / (256 * KSG_ST_NPT), 1),
-                      (cn + KSG_ST_PODS - 1) / KSG_ST_PODS);
-      hipLaunchKernelGGL(k_static, grid, dim3(256), 0, s, C, F, I.progs.p, I.prog_off_d.p, c0, cn, I.stat.p, I.mpred.p, 0);
-      for (uint32_t j = c0; j < c0 + cn; ++j) {
-        const uint8_t* prog = I.progs.p + I.prog_off[j];
-        const int mode = commit ? 1 : 0;
-        DevOut O{I.filter.p, I.score.p, I.total.p, I.sums.p + j, nullptr, mode, I.prow.p + j};
-        if (I.keep_n && j >= I.keep_first && j < I.keep_first + I.keep_n) {
-          size_t k = j - I.keep_first;
-          O.filter = I.kfilter.p + k * N;
-          O.score = I.kscore.p + k * N * KSG_MAX_PLUGINS;
-          O.total = I.ktotal.p + k * N;
-        }
-        bool sampled = I.sample_every && (j % I.sample_every) == 0 && I.n_samples * 2 + 2 <= I.sev.size();
-        if (sampled) HIPCHK(hipEventRecord(I.sev[I.n_samples * 2], s));
-        hipLaunchKernelGGL(k_fs_static, gN, b, 0, s, C, F, O, prog, I.stat.p + (size_t)(j - c0) * Nn,
-                           I.mpred.p + 2 * (size_t)(j - c0), I.saux.p);
-        if (sampled) {
-          HIPCHK(hipEventRecord(I.sev[I.n_samples * 2 + 1], s));
-          I.n_samples++;
-        }
-      }
-    }
-    HIPCHK(hipEventRecord(I.ev1, s));
-    HIPCHK(hipGetLastError());
-    return true;
-  }
-  const XLay XL{I.nsp, I.spair.p, I.uniq};
-  // one exchange point: pack (device), all-gather, merge (device)
-  auto xrun = [&](size_t len, auto pack, auto merge) -> bool {
-    const size_t bytes = std::max<size_t>(len, 1) * sizeof(int64_t);
-    if (!I.xsend.grow(bytes, 0, s, err) || !I.xrecv.grow(bytes * I.xranks, 0, s, err)) return false;
-    pack(reinterpret_cast<int64_t*>(I.xsend.p));
-    if (!xgather(I, bytes, err)) return false;
-    merge(reinterpret_cast<const int64_t*>(I.xrecv.p));
-    return true;
-  };
-  const uint32_t xr = I.xranks;
-  // table chain (table_chain.hip): pod index on the device, partials per block
-  ChainArgs CA{};
+    if (F.plugins[i] == KP_PTS) Q.pts_pos = i;
+  Q.XL = XLay{I.nsp, I.spair.p, I.uniq};
+  ChainArgs& CA = Q.CA;
+  CA = ChainArgs{};
   CA.progs = I.progs.p;
   CA.prog_off = I.prog_off_d.p;
   CA.sums = I.sums.p;
@@ -7833,266 +7879,286 @@ bool Engine::run_queue(uint32_t first, uint32_t count, bool commit, std::string&
   CA.filter = I.filter.p; CA.score = I.score.p; CA.total = I.total.p;
   CA.nblk = I.cnblk;
   CA.pi = I.cpi.p; CA.pm = I.cpm.p; CA.pr = I.cpr.p; CA.pm2 = I.cpm2.p; CA.pk = I.cpk.p; CA.pst = I.cpst.p;
-  CA.mode = commit ? (1 | ((I.has_pts || I.has_ipa) ? 2 : 0)) : 0;
+  CA.mode = Q.commit ? (1 | ((I.has_pts || I.has_ipa) ? 2 : 0)) : 0;
   CA.prow = I.prow.p;
   CA.need_eph = I.any_eph_req ? 1u : 0u;
-  if (!I.alog.alloc(std::max<uint32_t>(count, 1), err)) return false;
+  if (!I.alog.alloc(std::max<uint32_t>(Q.count, 1), err)) return false;
   CA.alog = I.alog.p;
-  CA.log_base = first;
+  CA.log_base = Q.first;
   CA.arrive = I.carrive.p;
   CA.stamps = I.cstamps_on ? I.cstamps.p : nullptr;
   CA.etot = nullptr;
   CA.xsend = nullptr;
-  if (I.cnblk > I.fold_blocks || xchain) {  // fold k_eval's partials once (k_fold, or the X2 merge) above this many blocks
+  if (I.cnblk > I.fold_blocks || Q.xchain) {  // fold k_eval's partials once (k_fold, or the X2 merge) above this many blocks
     if (!I.cetot.alloc(1, err)) return false;
     CA.etot = I.cetot.p;
   }
-  if (xchain) {  // node-sharded table chain: the X2 / X3 / X4 records
+  if (Q.xchain) {  // node-sharded table chain: the X2 / X3 / X4 records
     const size_t xb = (size_t)kX2 * sizeof(int64_t);
     if (!I.xsend.grow(xb, 0, s, err) || !I.xrecv.grow(xb * I.xranks, 0, s, err)) return false;
   }
-  int64_t* const xs = reinterpret_cast<int64_t*>(I.xsend.p);
-  const int64_t* const xrv = reinterpret_cast<const int64_t*>(I.xrecv.p);
-  const int rowm = I.R > 4 ? 0 : (I.eval_mode == 1 ? 2 : 1);
-  bool pending = false;           // logged assumes whose existing-pod table rows are not written yet
-  // rows of the logged pods [log_base, j); the log restarts at `next` (a pod of the
-  // scanning chain is not logged: the log restarts after it)
-  auto flush = [&](uint32_t j, uint32_t next) {
-    if (pending) hipLaunchKernelGGL(k_flush_appends, dim3(1), b, 0, s, C, CA, j - CA.log_base);
-    pending = false;
-    CA.log_base = next;
-  };
-  uint32_t pmask = 0;  // the profile's device plugins (kernel specialisations)
-  for (int i = 0; i < F.n; ++i) pmask |= 1u << F.plugins[i];
-  if (__builtin_popcount(pmask) != F.n) pmask = ~0u;  // (a plugin at two positions: the generic kernels, kNPos)
+  Q.xs = reinterpret_cast<int64_t*>(I.xsend.p);
+  Q.xrv = reinterpret_cast<const int64_t*>(I.xrecv.p);
+  Q.rowm = I.R > 4 ? 0 : (I.eval_mode == 1 ? 2 : 1);
+  Q.pmask = 0;
+  for (int i = 0; i < F.n; ++i) Q.pmask |= 1u << F.plugins[i];
+  if (__builtin_popcount(Q.pmask) != F.n) Q.pmask = ~0u;  // (a plugin at two positions: the generic kernels, kNPos)
   // persistent segments (k_chain_run): consecutive eligible pods in one launch
-  auto kept_pod = [&](uint32_t j) { return I.keep_n && j >= I.keep_first && j < I.keep_first + I.keep_n; };
-  bool run_ok = commit && !xchain && F.has_ext && rowm != 0 && I.run_on != 0;
-  if (run_ok && !I.run_cap) {
-    int occ1 = 0, occ2 = 0;
-    int occ3 = 0, occ4 = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ1, k_chain_run<1, ~0u>, kChain, 0));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ2, k_chain_run<2, ~0u>, kChain, 0));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ3, k_chain_run<2, kPmTab>, kChain, 0));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ4, k_chain_run<2, kPmTabTN>, kChain, 0));
-    int occ5 = 0, occ6 = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ5, (k_chain_run<2, kPmTab, kRunLK, kRunTS>), kChain, 0));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ6, (k_chain_run<2, kPmTab, kRunLK, kRunTS, 512>), 512, 0));
-    const int occ = std::min(std::min(std::min(occ1, occ2), std::min(occ3, occ4)), occ5);
-    I.run_cap512 = occ6 <= 0 ? 0u : I.n_cus * (uint32_t)(occ6 >= 2 ? occ6 - 1 : occ6);
-    // (MI355X_MICROARCH.md: the hardware may admit one block per CU fewer than the query)
-    I.run_cap = occ <= 0 ? 1u : I.n_cus * (uint32_t)(occ >= 2 ? occ - 1 : occ);
-    if (occ <= 0) I.run_on = 0;
+  Q.run_ok = Q.commit && !Q.xchain && F.has_ext && Q.rowm != 0 && I.run_on != 0;
+  if (Q.run_ok && !I.run_cap) {
+    if (!chain_run_cap(I, I.run_cap, err)) return false;
+    if (!I.run_cap) {
+      I.run_cap = 1;
+      I.run_on = 0;
+    }
   }
-  // 512-thread blocks (KSG_RUN_BT=512): half the blocks, for the small size class of the cfg4 plugin set
-  const uint32_t nb512 = (I.N + 511) / 512;
-  const bool bt512 = I.run_bt == 512 && (pmask & ~kPmTab) == 0 && rowm == 2 && nb512 + 1 <= I.run_cap512 && nb512 <= (uint32_t)kChain;
-  run_ok = run_ok && I.run_on != 0 && I.cnblk + 1 <= I.run_cap && I.cnblk <= (uint32_t)kChain;  // (+1: the committer)
-  auto run_elig = [&](uint32_t j) {
-    const uint32_t nd = I.prog_need[j];
-    return (nd & 4) && !(nd & 8) && (nd & (1u << 17)) && !kept_pod(j);
-  };
-  if (run_ok) {
+  Q.run_ok = Q.run_ok && I.run_on != 0 && I.cnblk + 1 <= I.run_cap && I.cnblk <= (uint32_t)kChain;  // (+1: the committer)
+  if (Q.run_ok) {
     if (!I.rsync.alloc(1, err) || !I.rgran.alloc(4 * kRunSlot, err)) return false;
     if (!I.hverdict) {
       HIPCHK(hipHostMalloc((void**)&I.hverdict, kVerdictBytes, hipHostMallocCoherent | hipHostMallocMapped));
       HIPCHK(hipMemsetAsync(I.rsync.p, 0, sizeof(RunSync), s));  // (the sticky abort word starts clear)
     }
   }
-  for (uint32_t j = first; j < first + count; ++j) {
-    const uint8_t* prog = I.progs.p + I.prog_off[j];
-    if (run_ok && run_elig(j)) {
-      // a segment: consecutive eligible pods of one size class
-      const uint32_t cls = I.prog_need[j] & (1u << 18);
-      uint32_t j1 = j + 1;
-      while (j1 < first + count && run_elig(j1) && (I.prog_need[j1] & (1u << 18)) == cls) ++j1;
-      if (j1 - j >= I.run_min) {
-        CA.q = j;
-        CA.prog = prog;
-        CA.xsend = nullptr;
-        ChainArgs RA = CA;  // (stamps: k_chain_run's own slots)
-        HIPCHK(hipMemsetAsync(I.rsync.p, 0, kRunSyncReset, s));
-        HIPCHK(hipMemsetAsync(I.rgran.p, 0, 4 * kRunSlot * sizeof(uint64_t), s));
-        const bool sampled = I.sample_every && I.n_samples * 2 + 2 <= I.sev.size();
-        if (sampled) HIPCHK(hipEventRecord(I.sev[I.n_samples * 2], s));
-        uint64_t* const g1 = I.rgran.p;
-        uint64_t* const g2 = I.rgran.p + 2 * kRunSlot;
-        const bool l512 = bt512 && cls;
-        const uint32_t grid = (l512 ? nb512 : I.cnblk) + 1;  // node blocks + the committer
-        uint32_t* const hv = I.hverdict;
-        __atomic_store_n(hv, 0u, __ATOMIC_RELEASE);  // (the previous segment's verdict was read)
-        const RunCtl RC{grid + I.run_need_extra, I.run_wait_us * 100u, I.run_lag, hv, I.run_spin, I.run_overlap ? 1u : 0u,
-                        I.run_defer ? 1u : 0u};
-        const dim3 gr(grid), bk(kChain);
-        if (l512) {
-          ChainArgs R5 = RA;
-          R5.nblk = nb512;
-          hipLaunchKernelGGL((k_chain_run<2, kPmTab, kRunLK, kRunTS, 512>), gr, dim3(512), 0, s, C, F, R5, j1 - j,
-                             I.rsync.p, g1, g2, RC, RA.progs, RA.prog_off);
-        } else if (rowm == 2 && (pmask & ~kPmTab) == 0 && cls)
-          hipLaunchKernelGGL((k_chain_run<2, kPmTab, kRunLK, kRunTS>), gr, bk, 0, s, C, F, RA, j1 - j, I.rsync.p, g1, g2, RC, RA.progs, RA.prog_off);
-        else if (rowm == 2 && (pmask & ~kPmTab) == 0)
-          hipLaunchKernelGGL((k_chain_run<2, kPmTab>), gr, bk, 0, s, C, F, RA, j1 - j, I.rsync.p, g1, g2, RC, RA.progs, RA.prog_off);
-        else if (rowm == 2 && (pmask & ~kPmTabTN) == 0)
-          hipLaunchKernelGGL((k_chain_run<2, kPmTabTN>), gr, bk, 0, s, C, F, RA, j1 - j, I.rsync.p, g1, g2, RC, RA.progs, RA.prog_off);
-        else if (rowm == 2) hipLaunchKernelGGL((k_chain_run<2, ~0u>), gr, bk, 0, s, C, F, RA, j1 - j, I.rsync.p, g1, g2, RC, RA.progs, RA.prog_off);
-        else hipLaunchKernelGGL((k_chain_run<1, ~0u>), gr, bk, 0, s, C, F, RA, j1 - j, I.rsync.p, g1, g2, RC, RA.progs, RA.prog_off);
-        if (sampled) {
-          HIPCHK(hipEventRecord(I.sev[I.n_samples * 2 + 1], s));
-          I.n_samples++;
-        }
-        HIPCHK(hipGetLastError());
-        I.run_used = true;
-        // The handshake: the launch's blocks decide whether all of them are
-        // resident before any state changes.  The host waits for that verdict (the
-        // work queued before the segment runs first), then queues the rest.
-        const uint32_t v = wait_verdict(I, s, err);
-        if (v == 0u) return false;
-        if (v == 3u) {  // an earlier segment of this call aborted: the state is not valid
-          I.lost = true;
-          err = "persistent table chain: a gate never completed (blocks not co-resident?)";
-          return false;
-        }
-        if (v == 1u) {
-          I.path_pods[0] += j1 - j;
-          I.path_pods[4] += j1 - j;
-          I.path_pods[5]++;
-          pending |= (CA.mode & 2) != 0;
+  return true;
+}
+
+// May pod j run in a persistent segment?
+static bool segment_pod(const Engine::Impl& I, uint32_t j) {
+  const uint32_t nd = I.prog_need[j];
+  return need::table(nd) && !need::pts_raw(nd) && need::segment(nd) && !kept_pod(I, j);
+}
+// The end of the segment that starts at pod j: consecutive eligible pods of one size class.
+static uint32_t segment_end(const Engine::Impl& I, const QueueRun& Q, uint32_t j) {
+  const bool cls = need::small_class(I.prog_need[j]);
+  uint32_t j1 = j + 1;
+  while (j1 < Q.first + Q.count && segment_pod(I, j1) && need::small_class(I.prog_need[j1]) == cls) ++j1;
+  return j1;
+}
+
+// One persistent segment, pods [j, j1): the launch, the handshake, its verdict.
+// ran: the segment ran; else (its blocks were not all resident and left
+// untouched) this and the call's later segments run on the two-launch chain.
+static bool queue_segment(Engine::Impl& I, QueueRun& Q, uint32_t j, uint32_t j1, bool& ran, std::string& err) {
+  hipStream_t s = Q.s;
+  ran = false;
+  Q.CA.q = j;
+  Q.CA.prog = I.progs.p + I.prog_off[j];
+  Q.CA.xsend = nullptr;
+  ChainArgs RA = Q.CA;  // (stamps: k_chain_run's own slots)
+  const bool cls = need::small_class(I.prog_need[j]);
+  const ChainRunVariant* const V = std::find_if(std::begin(kChainRun), std::end(kChainRun), [&](const ChainRunVariant& v) {
+    return v.rowm == Q.rowm && (Q.pmask & ~v.pmask) == 0 && (cls || !v.small_class);
+  });
+  if (V == std::end(kChainRun)) { err = "persistent table chain: no kernel for this profile"; return false; }
+  HIPCHK(hipMemsetAsync(I.rsync.p, 0, kRunSyncReset, s));
+  HIPCHK(hipMemsetAsync(I.rgran.p, 0, 4 * kRunSlot * sizeof(uint64_t), s));
+  bool sampled;
+  if (!sample_begin(I, s, true, sampled, err)) return false;
+  const uint32_t grid = RA.nblk + 1;  // node blocks + the committer
+  uint32_t* const hv = I.hverdict;
+  __atomic_store_n(hv, 0u, __ATOMIC_RELEASE);  // (the previous segment's verdict was read)
+  const RunCtl RC{grid + I.run_need_extra, I.run_wait_us * 100u, I.run_lag, hv, I.run_spin, I.run_defer ? 1u : 0u};
+  hipLaunchKernelGGL(V->fn, dim3(grid), dim3(kChain), 0, s, Q.C, I.F, RA, j1 - j, I.rsync.p, I.rgran.p,
+                     I.rgran.p + 2 * kRunSlot, RC, RA.progs, RA.prog_off);
+  if (!sample_end(I, s, sampled, err)) return false;
+  HIPCHK(hipGetLastError());
+  I.run_used = true;
+  // The handshake: the launch's blocks decide whether all of them are
+  // resident before any state changes.  The host waits for that verdict (the
+  // work queued before the segment runs first), then queues the rest.
+  const uint32_t v = wait_verdict(I, s, err);
+  if (v == 0u) return false;
+  if (v == 3u) {  // an earlier segment of this call aborted: the state is not valid
+    I.lost = true;
+    err = "persistent table chain: a gate never completed (blocks not co-resident?)";
+    return false;
+  }
+  if (v == 1u) {
+    I.path_pods[0] += j1 - j;
+    I.path_pods[4] += j1 - j;
+    I.path_pods[5]++;
+    Q.pending |= (Q.CA.mode & 2) != 0;
+    ran = true;
+    return true;
+  }
+  I.run_fallbacks++;  // v == 2
+  Q.run_ok = false;
+  return true;
+}
+
+// One cycle of the two-launch table chain: k_eval, then (profiles with
+// ScoreExtensions) k_fold / k_ptsraw / k_final; sharded, the X2..X4 exchanges.
+static bool queue_table_cycle(Engine::Impl& I, QueueRun& Q, uint32_t j, std::string& err) {
+  hipStream_t s = Q.s;
+  const DevCluster& C = Q.C;
+  const DevProfile& F = I.F;
+  ChainArgs& CA = Q.CA;
+  const uint8_t* prog = I.progs.p + I.prog_off[j];
+  const int rowm = Q.rowm;
+  const bool xchain = Q.xchain;
+  const uint32_t xr = I.xranks;
+  const dim3 gC(I.cnblk), bC(kChain);
+  I.path_pods[0]++;
+  CA.q = j;
+  CA.prog = prog;
+  CA.xsend = xchain ? Q.xs : nullptr;
+  bool sampled;
+  if (!sample_begin(I, s, every_nth(I, j), sampled, err)) return false;
+  const bool occ = I.cnblk > (I.occ_blocks ? I.occ_blocks : 2 * I.n_cus) || I.occ_force;  // many blocks per CU
+  if (occ) {
+    hipLaunchKernelGGL(rowm == 2 ? k_eval_occ<2> : rowm == 1 ? k_eval_occ<1> : k_eval_occ<0>, gC, bC, 0, s, C, F, CA, prog);
+  } else {
+    // (a fused view: the armed view of this pod when its cycle is this one launch)
+    ChainArgs CE = CA;
+    if (I.vp_armed && I.vp_q == j && !I.vp_fused && I.view_fuse && !F.has_ext && !xchain && I.vblk.p) {
+      CE.vf = I.vp_V;
+      CE.vf_out = I.vblk.p;
+      CE.vf_hout = I.vp_hout;
+      I.vp_fused = true;
+    }
+    hipLaunchKernelGGL(rowm == 2 ? k_eval<2> : rowm == 1 ? k_eval<1> : k_eval<0>, gC, bC, 0, s, C, F, CE, prog);
+  }
+  if (!sample_end(I, s, sampled, err)) return false;
+  if (F.has_ext) {  // (k_final's last block selects; without ScoreExtensions k_eval's)
+    if (xchain) {  // X2: the cycle's counts and normalisers over every rank
+      hipLaunchKernelGGL(k_tx2_pack, dim3(1), bC, 0, s, C, F, CA, prog, Q.xs);
+      if (!xgather(I, (size_t)kX2 * sizeof(int64_t), err)) return false;
+      hipLaunchKernelGGL(k_tx2_merge, dim3(1), dim3(64), 0, s, C, CA, prog, Q.xrv, xr);
+    } else if (CA.etot) {
+      hipLaunchKernelGGL(k_fold, dim3(1), bC, 0, s, C, F, CA, prog);
+    }
+    if (need::pts_raw(I.prog_need[j])) {
+      hipLaunchKernelGGL(k_ptsraw, gC, bC, 0, s, C, F, CA, prog);
+      if (xchain) {  // X3
+        hipLaunchKernelGGL(k_tx3_pack, dim3(1), bC, 0, s, CA, Q.xs);
+        if (!xgather(I, 2 * sizeof(int64_t), err)) return false;
+        hipLaunchKernelGGL(k_tx3_merge, dim3(1), bC, 0, s, CA, Q.xrv, xr);
+      }
+    }
+    if (occ) hipLaunchKernelGGL(k_final_occ, gC, bC, 0, s, C, F, CA, prog);
+    else if ((Q.pmask & ~kPmTab) == 0)  // (the plugin-set specialisation: kNPos)
+      hipLaunchKernelGGL(k_final<kPmTab>, gC, bC, 0, s, C, F, CA, prog);
+    else hipLaunchKernelGGL(k_final<>, gC, bC, 0, s, C, F, CA, prog);
+  }
+  if (xchain) {  // X4: selectHost over the ranks, the assume split by ownership
+    if (!xgather(I, 3 * sizeof(int64_t), err)) return false;
+    hipLaunchKernelGGL(k_tx4_select, dim3(1), dim3(64), 0, s, C, F, CA, prog, Q.xrv, xr);
+  }
+  Q.pending |= (CA.mode & 2) != 0;
+  return true;
+}
+
+// One cycle of the scanning chain (k_begin .. k_finalize): the pod's domain
+// counts from a scan of the existing-pod table; sharded, the X1..X4 exchanges.
+static bool queue_scan_cycle(Engine::Impl& I, QueueRun& Q, uint32_t j, std::string& err) {
+  hipStream_t s = Q.s;
+  const DevCluster& C = Q.C;
+  const DevScratch& S = Q.S;
+  const DevProfile& F = I.F;
+  const XLay& XL = Q.XL;
+  const uint8_t* prog = I.progs.p + I.prog_off[j];
+  const bool xchain = Q.xchain;
+  const uint32_t xr = I.xranks, N = I.N;
+  const dim3 gN((N + kBlock - 1) / kBlock), b(kBlock);
+  // one exchange point: pack (device), all-gather, merge (device)
+  auto xrun = [&](size_t len, auto pack, auto merge) -> bool {
+    const size_t bytes = std::max<size_t>(len, 1) * sizeof(int64_t);
+    if (!I.xsend.grow(bytes, 0, s, err) || !I.xrecv.grow(bytes * I.xranks, 0, s, err)) return false;
+    pack(reinterpret_cast<int64_t*>(I.xsend.p));
+    if (!xgather(I, bytes, err)) return false;
+    merge(reinterpret_cast<const int64_t*>(I.xrecv.p));
+    return true;
+  };
+  queue_flush(Q, j, j + 1);  // the scanning chain reads the existing-pod table
+  I.path_pods[1]++;
+  const int mode = Q.commit ? (1 | ((I.has_pts || I.has_ipa) ? 2 : 0)) : 0;
+  DevOut O{I.filter.p, I.score.p, I.total.p, I.sums.p + j, xchain ? nullptr : I.arrive1.p, mode, I.prow.p + j};
+  kept_outputs(I, j, O);
+  const bool pts = I.has_pts && need::pts(I.prog_need[j]);
+  const bool ipa = I.has_ipa;
+  if (pts || ipa) {
+    uint32_t work = std::max<uint32_t>(KSG_MAX_TSC * N, I.topo.topo_pairs);
+    uint32_t gb = std::min<uint32_t>((work + kBlock - 1) / kBlock, 2048);
+    hipLaunchKernelGGL(k_begin, dim3(std::max<uint32_t>(gb, 1)), b, 0, s, C, S, prog);
+    uint32_t pc = I.pcap;  // grid covers capacity; kernel reads the live count
+    hipLaunchKernelGGL(k_scan_pods, dim3((pc + kBlock - 1) / kBlock), b, 0, s, C, F, S, O, prog);
+    if (ipa)
+      hipLaunchKernelGGL(k_scan_terms, dim3((I.tcap + kBlock - 1) / kBlock), b, 0, s, C, F, S, O, prog);
+    const dim3 gr(std::max<uint32_t>(std::min<uint32_t>(gN.x, 256), 1));
+    if (pts) {
+      hipLaunchKernelGGL(k_pts_prep, gN, b, 0, s, C, S, prog);
+      hipLaunchKernelGGL(k_pts_reduce, gr, b, 0, s, C, S, prog, xchain ? I.uniq : ~0u);
+    }
+    if (xchain) {  // X1
+      const size_t len = (size_t)7 * I.nsp + 2 + 2 * KSG_MAX_TOPO;
+      if (!xrun(len, [&](int64_t* o) { hipLaunchKernelGGL(k_x1_pack, dim3(1), b, 0, s, S, O, XL, o); },
+                [&](const int64_t* r) { hipLaunchKernelGGL(k_x1_merge, dim3(1), b, 0, s, S, O, XL, r, xr); }))
+        return false;
+      if (pts) hipLaunchKernelGGL(k_pts_reduce, gr, b, 0, s, C, S, prog, ~I.uniq);
+    }
+  }
+  bool sampled;
+  if (!sample_begin(I, s, every_nth(I, j), sampled, err)) return false;
+  hipLaunchKernelGGL(k_filter_score, gN, b, 0, s, C, F, S, O, prog);
+  if (!sample_end(I, s, sampled, err)) return false;
+  if (xchain) {  // X2
+    const size_t len = 3 + 2 * KSG_MAX_PLUGINS + (size_t)I.nsp + KSG_MAX_TSC;
+    if (!xrun(len, [&](int64_t* o) { hipLaunchKernelGGL(k_x2_pack, dim3(1), b, 0, s, C, S, O, prog, XL, o); },
+              [&](const int64_t* r) {
+                hipLaunchKernelGGL(k_x2_merge, dim3(1), b, 0, s, S, O, XL, r, xr, I.xregcnt.p);
+              }))
+      return false;
+  }
+  if (F.has_ext) {
+    if (Q.pts_pos >= 0 && pts) {
+      hipLaunchKernelGGL(k_pts_weights, dim3(1), b, 0, s, C, S, O, prog, xchain ? I.xregcnt.p : nullptr, I.uniq);
+      hipLaunchKernelGGL(k_pts_score, gN, b, 0, s, C, S, O, prog, Q.pts_pos);
+      if (xchain &&  // X3
+          !xrun(2 * KSG_MAX_PLUGINS, [&](int64_t* o) { hipLaunchKernelGGL(k_x3_pack, dim3(1), b, 0, s, O, o); },
+                [&](const int64_t* r) { hipLaunchKernelGGL(k_x3_merge, dim3(1), b, 0, s, O, r, xr); }))
+        return false;
+    }
+    hipLaunchKernelGGL(k_finalize, gN, b, 0, s, C, F, S, O, prog);
+  }
+  if (xchain) {  // X4, then selectHost + assume on the owner of the node
+    if (!xrun(2, [&](int64_t* o) { hipLaunchKernelGGL(k_x4_pack, dim3(1), b, 0, s, O, o); },
+              [&](const int64_t* r) { hipLaunchKernelGGL(k_x4_merge, dim3(1), b, 0, s, O, r, xr); }))
+      return false;
+    hipLaunchKernelGGL(k_commit, dim3(1), dim3(64), 0, s, C, F, O, prog, mode, I.prow.p + j);
+  }
+  // unsharded: selectHost + assume folded into the last block of the cycle's last kernel
+  return true;
+}
+
+bool Engine::run_queue(uint32_t first, uint32_t count, bool commit, std::string& err) {
+  Impl& I = *p_;
+  if (first + count > I.prog_off.size()) { err = "program index out of range"; return false; }
+  if (!tables_ready(I, err)) return false;
+  if (commit && batch_path()) return run_batches(I, first, count, err);
+  hipStream_t s = I.stream;
+  if (I.sample_every && !ensure_sample_events(I, 2 * ((count + I.sample_every - 1) / I.sample_every + 1), err)) return false;
+  I.n_samples = 0;
+  HIPCHK(hipEventRecord(I.ev0, s));
+  QueueRun Q{first, count, commit, s, I.cluster(), I.scratch(), I.xranks > 1};
+  if (I.static_ok && I.static_fits && !Q.xchain) {
+    if (!queue_static_chain(I, first, count, commit, err)) return false;
+  } else {
+    if (!queue_setup(I, Q, err)) return false;
+    for (uint32_t j = first; j < first + count; ++j) {
+      if (Q.run_ok && segment_pod(I, j)) {
+        const uint32_t j1 = segment_end(I, Q, j);
+        bool ran = false;
+        if (j1 - j >= I.run_min && !queue_segment(I, Q, j, j1, ran, err)) return false;
+        if (ran) {
           j = j1 - 1;
           continue;
         }
-        // v == 2: the blocks were not all resident; they left untouched.  This and
-        // the call's later segments run on the two-launch chain.
-        I.run_fallbacks++;
-        run_ok = false;
       }
+      if (need::table(I.prog_need[j]) ? !queue_table_cycle(I, Q, j, err) : !queue_scan_cycle(I, Q, j, err)) return false;
     }
-    if (I.prog_need[j] & 4) {
-      I.path_pods[0]++;
-      CA.q = j;
-      CA.prog = prog;
-      CA.xsend = xchain ? xs : nullptr;
-      const bool sampled = I.sample_every && (j % I.sample_every) == 0 && I.n_samples * 2 + 2 <= I.sev.size();
-      if (sampled) HIPCHK(hipEventRecord(I.sev[I.n_samples * 2], s));
-      const bool occ = I.cnblk > (I.occ_blocks ? I.occ_blocks : 2 * I.n_cus) || I.occ_force;  // many blocks per CU
-      if (occ) {
-        if (rowm == 2) hipLaunchKernelGGL(k_eval_occ<2>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
-        else if (rowm == 1) hipLaunchKernelGGL(k_eval_occ<1>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
-        else hipLaunchKernelGGL(k_eval_occ<0>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
-      } else {
-        // (a fused view: the armed view of this pod when its cycle is this one launch)
-        ChainArgs CE = CA;
-        if (I.vp_armed && I.vp_q == j && !I.vp_fused && I.view_fuse && !F.has_ext && !xchain && I.vblk.p) {
-          CE.vf = I.vp_V;
-          CE.vf_out = I.vblk.p;
-          CE.vf_hout = I.vp_hout;
-          I.vp_fused = true;
-        }
-        if (rowm == 2) hipLaunchKernelGGL(k_eval<2>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CE, prog);
-        else if (rowm == 1) hipLaunchKernelGGL(k_eval<1>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CE, prog);
-        else hipLaunchKernelGGL(k_eval<0>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CE, prog);
-      }
-      if (sampled) {
-        HIPCHK(hipEventRecord(I.sev[I.n_samples * 2 + 1], s));
-        I.n_samples++;
-      }
-      if (F.has_ext) {  // (k_final's last block selects; without ScoreExtensions k_eval's)
-        if (xchain) {  // X2: the cycle's counts and normalisers over every rank
-          hipLaunchKernelGGL(k_tx2_pack, dim3(1), dim3(kChain), 0, s, C, F, CA, prog, xs);
-          if (!xgather(I, (size_t)kX2 * sizeof(int64_t), err)) return false;
-          hipLaunchKernelGGL(k_tx2_merge, dim3(1), dim3(64), 0, s, C, CA, prog, xrv, xr);
-        } else if (CA.etot) {
-          hipLaunchKernelGGL(k_fold, dim3(1), dim3(kChain), 0, s, C, F, CA, prog);
-        }
-        if (I.prog_need[j] & 8) {
-          hipLaunchKernelGGL(k_ptsraw, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
-          if (xchain) {  // X3
-            hipLaunchKernelGGL(k_tx3_pack, dim3(1), dim3(kChain), 0, s, CA, xs);
-            if (!xgather(I, 2 * sizeof(int64_t), err)) return false;
-            hipLaunchKernelGGL(k_tx3_merge, dim3(1), dim3(kChain), 0, s, CA, xrv, xr);
-          }
-        }
-        if (occ) hipLaunchKernelGGL(k_final_occ, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
-        else if ((pmask & ~kPmTab) == 0)  // (the plugin-set specialisation: kNPos)
-          hipLaunchKernelGGL(k_final<kPmTab>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
-        else hipLaunchKernelGGL(k_final<>, dim3(I.cnblk), dim3(kChain), 0, s, C, F, CA, prog);
-      }
-      if (xchain) {  // X4: selectHost over the ranks, the assume split by ownership
-        if (!xgather(I, 3 * sizeof(int64_t), err)) return false;
-        hipLaunchKernelGGL(k_tx4_select, dim3(1), dim3(64), 0, s, C, F, CA, prog, xrv, xr);
-      }
-      pending |= (CA.mode & 2) != 0;
-      continue;
-    }
-    flush(j, j + 1);  // the scanning chain reads the existing-pod table
-    I.path_pods[1]++;
-    const int mode = commit ? (1 | ((I.has_pts || I.has_ipa) ? 2 : 0)) : 0;
-    DevOut O{I.filter.p, I.score.p, I.total.p, I.sums.p + j, xchain ? nullptr : I.arrive1.p, mode, I.prow.p + j};
-    bool kept = I.keep_n && j >= I.keep_first && j < I.keep_first + I.keep_n;
-    if (kept) {
-      size_t k = j - I.keep_first;
-      O.filter = I.kfilter.p + k * N;
-      O.score = I.kscore.p + k * N * KSG_MAX_PLUGINS;
-      O.total = I.ktotal.p + k * N;
-    }
-    bool pts = I.has_pts && (I.prog_need[j] & 1);
-    bool ipa = I.has_ipa;
-    if (pts || ipa) {
-      uint32_t work = std::max<uint32_t>(KSG_MAX_TSC * N, I.topo.topo_pairs);
-      uint32_t gb = std::min<uint32_t>((work + kBlock - 1) / kBlock, 2048);
-      hipLaunchKernelGGL(k_begin, dim3(std::max<uint32_t>(gb, 1)), b, 0, s, C, S, prog);
-      uint32_t pc = I.pcap;  // grid covers capacity; kernel reads the live count
-      hipLaunchKernelGGL(k_scan_pods, dim3((pc + kBlock - 1) / kBlock), b, 0, s, C, F, S, O, prog);
-      if (ipa)
-        hipLaunchKernelGGL(k_scan_terms, dim3((I.tcap + kBlock - 1) / kBlock), b, 0, s, C, F, S, O, prog);
-      const dim3 gr(std::max<uint32_t>(std::min<uint32_t>(gN.x, 256), 1));
-      if (pts) {
-        hipLaunchKernelGGL(k_pts_prep, gN, b, 0, s, C, S, prog);
-        hipLaunchKernelGGL(k_pts_reduce, gr, b, 0, s, C, S, prog, xchain ? I.uniq : ~0u);
-      }
-      if (xchain) {  // X1
-        const size_t len = (size_t)7 * I.nsp + 2 + 2 * KSG_MAX_TOPO;
-        if (!xrun(len, [&](int64_t* o) { hipLaunchKernelGGL(k_x1_pack, dim3(1), b, 0, s, S, O, XL, o); },
-                  [&](const int64_t* r) { hipLaunchKernelGGL(k_x1_merge, dim3(1), b, 0, s, S, O, XL, r, xr); }))
-          return false;
-        if (pts) hipLaunchKernelGGL(k_pts_reduce, gr, b, 0, s, C, S, prog, ~I.uniq);
-      }
-    }
-    bool sampled = I.sample_every && (j % I.sample_every) == 0 && I.n_samples * 2 + 2 <= I.sev.size();
-    if (sampled) HIPCHK(hipEventRecord(I.sev[I.n_samples * 2], s));
-    hipLaunchKernelGGL(k_filter_score, gN, b, 0, s, C, F, S, O, prog);
-    if (sampled) {
-      HIPCHK(hipEventRecord(I.sev[I.n_samples * 2 + 1], s));
-      I.n_samples++;
-    }
-    if (xchain) {  // X2
-      const size_t len = 3 + 2 * KSG_MAX_PLUGINS + (size_t)I.nsp + KSG_MAX_TSC;
-      if (!xrun(len, [&](int64_t* o) { hipLaunchKernelGGL(k_x2_pack, dim3(1), b, 0, s, C, S, O, prog, XL, o); },
-                [&](const int64_t* r) {
-                  hipLaunchKernelGGL(k_x2_merge, dim3(1), b, 0, s, S, O, XL, r, xr, I.xregcnt.p);
-                }))
-        return false;
-    }
-    if (F.has_ext) {
-      if (pts_pos >= 0 && pts) {
-        hipLaunchKernelGGL(k_pts_weights, dim3(1), b, 0, s, C, S, O, prog, xchain ? I.xregcnt.p : nullptr, I.uniq);
-        hipLaunchKernelGGL(k_pts_score, gN, b, 0, s, C, S, O, prog, pts_pos);
-        if (xchain &&  // X3
-            !xrun(2 * KSG_MAX_PLUGINS, [&](int64_t* o) { hipLaunchKernelGGL(k_x3_pack, dim3(1), b, 0, s, O, o); },
-                  [&](const int64_t* r) { hipLaunchKernelGGL(k_x3_merge, dim3(1), b, 0, s, O, r, xr); }))
-          return false;
-      }
-      hipLaunchKernelGGL(k_finalize, gN, b, 0, s, C, F, S, O, prog);
-    }
-    if (xchain) {  // X4, then selectHost + assume on the owner of the node
-      if (!xrun(2, [&](int64_t* o) { hipLaunchKernelGGL(k_x4_pack, dim3(1), b, 0, s, O, o); },
-                [&](const int64_t* r) { hipLaunchKernelGGL(k_x4_merge, dim3(1), b, 0, s, O, r, xr); }))
-        return false;
-      hipLaunchKernelGGL(k_commit, dim3(1), dim3(64), 0, s, C, F, O, prog, mode, I.prow.p + j);
-    }
-    // unsharded: selectHost + assume folded into the last block of the cycle's last kernel
+    queue_flush(Q, first + count, first + count);
   }
-  flush(first + count, first + count);
   HIPCHK(hipEventRecord(I.ev1, s));
   HIPCHK(hipGetLastError());
   return true;
@@ -8159,7 +8225,7 @@ bool Engine::summaries(uint32_t first, uint32_t count, ksg_pod_summary* out, std
 
 bool Engine::outputs(uint32_t j, PodOutputs& out, std::string& err) {
   Impl& I = *p_;
-  if (!(I.keep_n && j >= I.keep_first && j < I.keep_first + I.keep_n)) { err = "outputs not kept for this pod"; return false; }
+  if (!kept_pod(I, j)) { err = "outputs not kept for this pod"; return false; }
   size_t N = I.N, k = j - I.keep_first;
   out.filter.resize(N);
   out.score.resize(N * KSG_MAX_PLUGINS);

@@ -577,18 +577,6 @@ struct EvalOut {
   ChainRec rec;
 };
 enum { kEval = 0, kRun = 1 };  // eval_body modes: k_eval, k_chain_run
-// k_chain_run's evaluation in two stages (eval_body STG): 1 issues every
-// class-table read of the node (the lookup plan, minMatchNum candidates,
-// InterPodAffinity map totals) and leaves the values in flight in an EvalPre;
-// 2 finishes from it (row-only plugins on the row as of then, filters, scores,
-// the block's record).  0: both at once.
-struct EvalPre {
-  int32_t lkv[KSG_LK_MAX], lks[KSG_LK_MAX];
-  uint8_t mpn[KSG_MAX_TSC];
-  int32_t mcnt[KSG_MAX_TSC];
-  int32_t ubv;
-  uint32_t ubbit;
-};
 // Class-table reads: plain loads in a launch of one cycle; in the persistent chain
 // the tables change under the launch (other blocks' assumes), so every read is an
 // agent-scope (sc1) load of what the assuming block wrote by atomics
@@ -633,14 +621,12 @@ __device__ __forceinline__ void row_pre(const RowV& row, const DevProfile& F, co
   }
   if (PMH(KP_BA)) o.bs = ROWM == 2 ? ba_score_row<1>(row, F, h) : ba_score_row<0>(row, F, h);
 }
-template <int ROWM, int MODE = kEval, uint32_t PM = ~0u, int LK = KSG_LK_MAX, int TS = KSG_MAX_TSC, int BT = kChain,
-          int STG = 0>
+template <int ROWM, int MODE = kEval, uint32_t PM = ~0u, int LK = KSG_LK_MAX, int TS = KSG_MAX_TSC, int BT = kChain>
 __device__ __forceinline__ void eval_body(DevCluster& C, const DevProfile& F, const ChainArgs& A,
                                           const uint8_t* __restrict__ prog, EvalSharedT<BT>* Lrun = nullptr,
                                           RowV* rowrun = nullptr, EvalOut* eo = nullptr, const RunWait* W = nullptr,
-                                          EvalPre* pre = nullptr, const RowPre* rp = nullptr) {
+                                          const RowPre* rp = nullptr) {
   constexpr bool RUN = MODE == kRun;
-  static_assert(STG == 0 || RUN, "staged evaluation: the persistent chain only");
   static_assert(BT == kChain || RUN, "other block sizes: the persistent chain only");
   if constexpr (!RUN) chain_warm(prog);
   CS_BEGIN;
@@ -695,7 +681,7 @@ __device__ __forceinline__ void eval_body(DevCluster& C, const DevProfile& F, co
       fit_b = rp->fb;
       fit_s = rp->fs;
       ba_s = rp->bs;
-    } else if (STG != 1) {  // (staged: on the row as of the finish)
+    } else {
       if (PMH(KP_FIT)) {
         fit_b = fit_filter_row(row, h, C.R);
         fit_s = ROWM == 2 ? fit_score_row<1>(row, F, h) : fit_score_row<0>(row, F, h);
@@ -703,7 +689,7 @@ __device__ __forceinline__ void eval_body(DevCluster& C, const DevProfile& F, co
       if (PMH(KP_BA)) ba_s = ROWM == 2 ? ba_score_row<1>(row, F, h) : ba_score_row<0>(row, F, h);
     }
     CS(14);
-    if (STG != 2 && W && !run_wait_flag(*W)) {
+    if (W && !run_wait_flag(*W)) {
       eo->abort = true;
       return;
     }
@@ -715,10 +701,7 @@ __device__ __forceinline__ void eval_body(DevCluster& C, const DevProfile& F, co
   for (int c = 0; c < TS; ++c) {
     mpn[c] = 0;
     mcnt[c] = 0;
-    if constexpr (STG == 2) {
-      mpn[c] = pre->mpn[c];
-      mcnt[c] = pre->mcnt[c];
-    } else if (pts_f && c < nf && threadIdx.x < (uint32_t)h->tsc[c].nvals) {
+    if (pts_f && c < nf && threadIdx.x < (uint32_t)h->tsc[c].nvals) {
       const ksg_tsc& t = h->tsc[c];
       mpn[c] = C.T.pair_node[t.pair_base + threadIdx.x];
       if (t.eff_cls >= 0) mcnt[c] = ld_tab<MODE>(C.T.pc_dom + (size_t)t.eff_cls * C.T.NU + (uint32_t)t.nub + threadIdx.x);
@@ -726,10 +709,7 @@ __device__ __forceinline__ void eval_body(DevCluster& C, const DevProfile& F, co
   }
   int32_t ubv = 0;
   uint32_t ubbit = 0;
-  if constexpr (STG == 2) {
-    ubv = pre->ubv;
-    ubbit = pre->ubbit;
-  } else if (ipa_pos >= 0 && h->n_ub > 0) {  // entry tid of the plan (uniform reads, then a per-lane pick)
+  if (ipa_pos >= 0 && h->n_ub > 0) {  // entry tid of the plan (uniform reads, then a per-lane pick)
     int32_t idx = 0, kind = 0;
 #pragma unroll
     for (int i = 0; i < KSG_UB_MAX; ++i) {
@@ -758,10 +738,7 @@ __device__ __forceinline__ void eval_body(DevCluster& C, const DevProfile& F, co
   for (int i = 0; i < LK; ++i) {
     lkv[i] = 0;
     lks[i] = -1;
-    if constexpr (STG == 2) {
-      lkv[i] = pre->lkv[i];
-      lks[i] = pre->lks[i];
-    } else if (i < h->n_lk) {
+    if (i < h->n_lk) {
       const ksg_look& e = h->lk[i];
       const uint32_t sku = e.sku;
       const int32_t kind = ksg_lk_kind(sku);
@@ -774,21 +751,6 @@ __device__ __forceinline__ void eval_body(DevCluster& C, const DevProfile& F, co
     }
   }
   CS(9);
-  if constexpr (STG == 1) {  // the reads are in flight: the caller finishes later (STG 2)
-#pragma unroll
-    for (int i = 0; i < LK; ++i) {
-      pre->lkv[i] = lkv[i];
-      pre->lks[i] = lks[i];
-    }
-#pragma unroll
-    for (int c = 0; c < TS; ++c) {
-      pre->mpn[c] = mpn[c];
-      pre->mcnt[c] = mcnt[c];
-    }
-    pre->ubv = ubv;
-    pre->ubbit = ubbit;
-    return;
-  }
   // ---- pod-uniform setup: minMatchNum per filter constraint, InterPodAffinity
   // bits — one interleaved block fold (one barrier; the results uniform in registers)
   uint32_t su[TS + 1];
@@ -1496,7 +1458,6 @@ struct RunCtl {
   uint32_t lag;            // diagnostic: the committer's s_sleep(127) rounds before each pod's granule reads
   uint32_t* host_verdict;  // pinned host word the deciding block writes (the host polls it), or null
   uint32_t spin;           // polls before a block gives up (kRunSpin; tests force an abort with few)
-  uint32_t overlap;        // issue pod k+1's class-table reads during pod k's hand-offs (KSG_RUN_OVERLAP)
   uint32_t defer;          // the owner's node-level assume after the next partial record when independent (KSG_RUN_DEFER)
   // blocks of another kernel this launch waits on (k_static_dec_run beside the window
   // loop: its blocks count themselves in here as they start); go only once side_need
@@ -1504,12 +1465,6 @@ struct RunCtl {
   const uint32_t* side_arrive;
   uint32_t side_need;
 };
-// Pod j+1 (header n) may read the class tables before pod j's (header h) assume:
-// it reads none of the pair-level nor node-level entries pod j writes (its row,
-// the only other change, is read only at the finish, after the assume).
-__device__ __forceinline__ bool run_indep(const ksg_prog* h, const ksg_prog* n) {
-  return (h->tab_md & n->tab_rd) == 0 && (h->nd_md & n->nd_rd) == 0;
-}
 constexpr uint32_t kRunSpin = 1u << 22;  // polls (~1 us each with the load) before a block gives up
 #ifndef KSG_RUN_SLEEP
 #define KSG_RUN_SLEEP 8
@@ -1727,15 +1682,8 @@ __device__ __forceinline__ void run_body(DevCluster& C, const DevProfile& F, con
   dfr_term.cls = -1;
   bool dfr_is_cls = false;
   bool dfr_any = false;  // (block-uniform: some lane holds a deferred item)
-  // Overlap (KSG_RUN_OVERLAP): when pod k+1 is independent of pod k (run_indep),
-  // its class-table reads are issued right after pod k's partial record goes out
-  // and stay in flight across pod k's fold, selection and assume; pod k+1 then
-  // finishes from them (eval_body stages 1 / 2) on its row as of then.
-  bool have = false;       // pre holds pod k's reads (issued during pod k-1)
-  EvalPre pre;
   RowPre rpre;             // pod k's row-only plugins, computed during pod k-1's key hand-off
   bool rpre_ok = false;
-  const ksg_prog* ph = nullptr;  // pod k-1's header
   for (uint32_t k = 0; k < count; ++k) {
     ChainArgs A = A0;  // (A.stamps: eval_body's own k_eval slots, block 0)
     A.q = A0.q + k;
@@ -1750,11 +1698,9 @@ __device__ __forceinline__ void run_body(DevCluster& C, const DevProfile& F, con
     // the class-table reads), its partial record
     EvalOut eo;
     eo.abort = false;
-    if (have) {
-      eval_body<ROWM, kRun, PM, LK, TS, BT, 2>(C, F, A, prog, &L, &row, &eo, nullptr, &pre);
-    } else {
+    {
       const RunWait W{Y, wait_for, &S.go, &S.seen, rs_on ? rst : nullptr, owned, R.spin};
-      eval_body<ROWM, kRun, PM, LK, TS, BT>(C, F, A, prog, &L, &row, &eo, &W, nullptr, rpre_ok ? &rpre : nullptr);
+      eval_body<ROWM, kRun, PM, LK, TS, BT>(C, F, A, prog, &L, &row, &eo, &W, rpre_ok ? &rpre : nullptr);
       owned = 0;
     }
     if (eo.abort) return;
@@ -1801,21 +1747,7 @@ __device__ __forceinline__ void run_body(DevCluster& C, const DevProfile& F, con
     RS(30);
     // diagnostic: the latest block's partial store (absolute clock, per pod parity)
     if (rst && threadIdx.x == 0) atomicMax((unsigned long long*)&rst[52 + (k & 1)], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-    // ---- pod k+1's class-table reads, in flight across this pod's hand-offs
-    const ksg_prog* nh = k + 1 < count ? reinterpret_cast<const ksg_prog*>(P + PO[A.q + 1]) : nullptr;
-    const bool tnext = R.overlap && nh && run_indep(h, nh);
-    if (tnext) {
-      ChainArgs A1 = A0;
-      A1.q = A.q + 1;
-      // the assumes before pod k (before pod k-1 when pod k+1 is independent of it too)
-      const RunWait W1{Y, (ph && run_indep(ph, nh)) ? (k ? k - 1 : 0u) : k, &S.go, &S.seen, nullptr, owned, R.spin};
-      EvalOut ea;
-      ea.abort = false;
-      eval_body<ROWM, kRun, PM, LK, TS, BT, 1>(C, F, A1, P + PO[A1.q], &L, &row, &ea, &W1, &pre);
-      if (ea.abort) return;
-      owned = 0;
-      if (rs_on) atomicAdd((unsigned long long*)&rst[40], 1ull);  // (pods whose reads went ahead)
-    }
+    const ksg_prog* nh = k + 1 < count ? reinterpret_cast<const ksg_prog*>(P + PO[A.q + 1]) : nullptr;  // pod k+1's header
     // ---- fold every block's partials (as reduce_eval)
     EvalTotals E;
     {
@@ -1889,10 +1821,9 @@ __device__ __forceinline__ void run_body(DevCluster& C, const DevProfile& F, con
       KWarm<0, kHdrBytes>::run(reinterpret_cast<const void*>(su), warm);
       warm_wait(warm);  // (the loads land in one scalar register the compiler may reuse: wait here)
     }
-    // the next pod's row-only plugins while the keys arrive (not when its reads go
-    // ahead: the staged evaluation computes them itself)
+    // the next pod's row-only plugins while the keys arrive
     rpre_ok = false;
-    if (nh && !tnext) {
+    if (nh) {
       row_pre<ROWM, PM>(row, F, view(P + PO[A.q + 1]).h, C.R, rpre);
       rpre_ok = true;
     }
@@ -1971,7 +1902,7 @@ __device__ __forceinline__ void run_body(DevCluster& C, const DevProfile& F, con
         row.podcnt += 1;
         if (rpre_ok) row_pre<ROWM, PM>(row, F, view(P + PO[A.q + 1]).h, C.R, rpre);  // (its row changed)
       }
-      const bool defer = R.defer && nh && !tnext && nitems <= (uint32_t)BT && (h->nd_md & nh->nd_rd) == 0;
+      const bool defer = R.defer && nh && nitems <= (uint32_t)BT && (h->nd_md & nh->nd_rd) == 0;
       if (defer) {
         if (C.T.on && threadIdx.x < nitems) {
           dfr_node = (uint32_t)node;
@@ -1998,9 +1929,7 @@ __device__ __forceinline__ void run_body(DevCluster& C, const DevProfile& F, con
     // the flag this block waits for before the next pod's class-table reads: every
     // assume up to this pod's if the next pod reads an entry this one writes
     // (tab_rd / tab_md), else every assume before this pod's
-    have = tnext;
-    if (nh && !tnext) wait_for = (node >= 0 && (h->tab_md & nh->tab_rd) != 0) ? tag : k;
-    ph = h;
+    if (nh) wait_for = (node >= 0 && (h->tab_md & nh->tab_rd) != 0) ? tag : k;
     RS(50);
     if (rs_on) atomicAdd((unsigned long long*)&rst[35], 1ull);
   }

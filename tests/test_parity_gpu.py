@@ -212,16 +212,15 @@ RUN_CASES = [
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env", [{}, {"KSG_RUN_MIN": "1"}, {"KSG_RUN_BT": "512"}, {"KSG_RUN_LAG": "4"},
-                                 {"KSG_RUN_OVERLAP": "1"}, {"KSG_RUN_DEFER": "0"}],
-                         ids=["default", "min1", "bt512", "lag", "overlap", "no-defer"])
+@pytest.mark.parametrize("env", [{}, {"KSG_RUN_MIN": "1"}, {"KSG_RUN_LAG": "4"}, {"KSG_RUN_DEFER": "0"}],
+                         ids=["default", "min1", "lag", "no-defer"])
 @pytest.mark.parametrize("name,c,sizes,keep", RUN_CASES, ids=[c[0] for c in RUN_CASES])
 def test_persistent_segments_match_oracle(monkeypatch, env, name, c, sizes, keep):
     """Persistent segments (k_chain_run: the pod loop inside one launch, gates
     between blocks) place every pod exactly as the oracle, with 1, 3 and 20
     blocks (XCD groups of unequal size), around kept pods that split a segment,
     and on a saturating cluster (unschedulable pods in the middle of a segment);
-    also with one-pod segments allowed (KSG_RUN_MIN=1), 512-thread blocks, and a
+    also with one-pod segments allowed (KSG_RUN_MIN=1), and a
     committer delayed ~14 us per pod (KSG_RUN_LAG=4: longer than a pod's evaluation,
     so the node blocks run a pod ahead of it and rewrite the granules of the pod
     after the one it reads; the parity-slotted granules keep those it reads), and
