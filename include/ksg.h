@@ -49,7 +49,8 @@ extern "C" {
  * 32-bit scores per position, built on the device.  4: its score rows are as
  * narrow as their values allow (score_bytes / normalized_bytes; ksg_view_score).
  * Added within 4 (no existing entry point or struct changed): ksg_ranked_nodes,
- * ksg_ranked_node, KSG_RANK_MAX. */
+ * ksg_ranked_node, KSG_RANK_MAX; ksg_filter_histogram, ksg_fit_error,
+ * ksg_filter_bucket, KSG_DIAG_MAX. */
 #define KSG_ABI_VERSION 4
 
 #define KSG_OK 0
@@ -306,6 +307,47 @@ typedef struct ksg_ranked_node {
   int32_t total;  /* its weighted score */
 } ksg_ranked_node;
 int ksg_ranked_nodes(ksg_ctx* ctx, uint32_t q, uint32_t k, ksg_ranked_node* out, uint32_t* n_out);
+/* Unschedulable diagnosis: why queue pod q's cycle found the nodes it found,
+ * counted on the device from the pod's kept outputs (valid for the pods
+ * ksg_ranked_nodes accepts).
+ * ksg_filter_histogram: the distinct (code, status) pairs over every local node,
+ * passed and not-evaluated nodes included, so the counts sum to the node count;
+ * ascending by (code, status), so two calls return the same bytes.  *n_out
+ * receives the number of buckets; cap too small: KSG_E_NOBUF with the needed
+ * count in *n_out.  A cycle can hold more than KSG_DIAG_MAX distinct pairs (every
+ * node its own taint): the call then counts the kept filter row on the host,
+ * with the same answer.  out or n_out NULL, q outside the queue: KSG_E_RANGE;
+ * outputs not kept for q: KSG_E_STATE (as ksg_normalized_scores); a sharded
+ * context: KSG_E_INVALID.  Changes no scheduling state.
+ * Env KSG_DIAG_SLOTS (read at ksg_create): slots of the device table, a power of
+ * two in [4, KSG_DIAG_MAX] (tests reach the host count with a handful of reasons).
+ * ksg_fit_error: the text of upstream v1.30.4 framework.FitError.Error() for an
+ * unschedulable pod (the PodScheduled condition's message),
+ *   "0/5000 nodes are available: 12 node(s) had untolerated taint {dedicated: gpu}, 4988 Insufficient cpu."
+ * up to but not including the PostFilter clause ("preemption: 0/N nodes are
+ * available: ..."), which needs per-node preemption statuses the dry run does not
+ * keep.  "0/<nodes of the snapshot> nodes are available:", then either the
+ * rejecting PreFilter's message (for an empty PreFilterResult intersection the
+ * framework's "node(s) didn't satisfy plugin(s) [A B] simultaneously" / "node(s)
+ * didn't satisfy plugin A") or, per distinct Filter reason (a NodeResourcesFit or
+ * VolumeBinding status splits into its reasons, each counted once per node),
+ * "<count> <reason>", the entries sorted as byte strings (sort.Strings: "10 x"
+ * before "2 x") and joined with ", "; a full stop closes a non-empty list.  Nodes
+ * outside the PreFilterResult are not counted.  A scheduled pod, or a cycle that
+ * ended in KSG_ERROR, gives *len = 0.  Buffer convention and codes of
+ * ksg_annotations (cap 0: the size in *len, KSG_E_NOBUF); otherwise the codes of
+ * ksg_filter_histogram. */
+#define KSG_DIAG_MAX 1024
+typedef struct ksg_filter_bucket {
+  uint32_t code;    /* device filter code, as ksg_filter_codes: KSG_FILTER_PASSED,
+                       KSG_FILTER_NOT_EVALUATED or (position << 24) | detail */
+  int32_t pos;      /* failing profile position; n_positions: passed; -1: not evaluated */
+  int32_t status;   /* framework.Code of that Filter failure (2 or 3), 0 passed, -1 not evaluated:
+                       what ksg_filter_status / the cycle view's fail_code give for these nodes */
+  uint32_t count;   /* local nodes with this (code, status) */
+} ksg_filter_bucket;
+int ksg_filter_histogram(ksg_ctx* ctx, uint32_t q, ksg_filter_bucket* out, uint32_t cap, uint32_t* n_out);
+int ksg_fit_error(ksg_ctx* ctx, uint32_t q, char* buf, size_t cap, size_t* len);
 /* PostFilter (wrappedplugin.go:550-577 -> store.go:442 AddPostFilterResult):
  * DefaultPreemption's dry run for an unschedulable pod q (PodEligibleToPreemptOthers,
  * nodesWherePreemptionMightHelp, SelectVictimsOnNode, pickOneNodeForPreemption of

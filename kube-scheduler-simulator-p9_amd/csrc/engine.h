@@ -10,6 +10,8 @@
 
 #include "ksg_types.h"
 
+struct ksg_filter_bucket;  // include/ksg.h
+
 namespace ksg {
 
 struct EngineConfig {
@@ -313,6 +315,22 @@ class Engine {
   };
   std::vector<KernelStat> kernel_stats() const;
 
+  // Unschedulable diagnosis (diagnosis.hip): what the device pass over a kept
+  // pod's filter row hands host.cpp's diag_call -- the distinct (code, status)
+  // pairs with their node counts, in no order, and the pod's summary; overflow:
+  // the device table could not hold every pair (entries is then not used: the
+  // host counts the row itself).  Plain data, no Engine member behind it.
+  struct DiagEntry {
+    uint32_t code;
+    int32_t status;
+    uint32_t count;
+  };
+  struct DiagCounts {
+    std::vector<DiagEntry> entries;
+    ksg_pod_summary summary;
+    bool overflow = false;
+  };
+
   struct Impl;
   Impl* impl() { return p_; }
 
@@ -320,6 +338,18 @@ class Engine {
   bool view_impl(uint32_t q, const ViewCfg& cfg, const ViewLayout& lay, uint8_t* host, std::string& err, bool wait,
                  bool arm);
   Impl* p_;
+};
+
+// What a diagnosis entry point (diagnosis.hip) asks of host.cpp's diag_call: the
+// buckets of ksg_filter_histogram, or (text) the sentence of ksg_fit_error.
+struct DiagRequest {
+  ::ksg_filter_bucket* out;
+  uint32_t cap;
+  uint32_t* n_out;
+  bool text;
+  char* buf;
+  size_t bcap;
+  size_t* len;
 };
 
 }  // namespace ksg

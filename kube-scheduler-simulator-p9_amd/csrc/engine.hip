@@ -5350,6 +5350,7 @@ struct DBuf {
 constexpr size_t kVerdictBytes = 64;
 constexpr size_t kVerdictAbortWord = 8;
 static_assert((kVerdictAbortWord + 1) * sizeof(uint32_t) <= kVerdictBytes, "the abort word lies inside the verdict block");
+constexpr uint32_t kDiagMax = 1024;   // unschedulable diagnosis: slots of the device count table (KSG_DIAG_MAX)
 constexpr uint32_t kRankTile = 2048;  // ranked candidates: most nodes (keys) one block of 256 threads selects from
 struct Engine::Impl {
   EngineConfig cfg;
@@ -5533,6 +5534,12 @@ struct Engine::Impl {
   uint32_t rank_tile = kRankTile;
   DBuf<uint64_t> rk_part;
   uint8_t* rk_host = nullptr;
+  // unschedulable diagnosis (diagnosis.hip): slots of the device count table in use (KSG_DIAG_SLOTS: a
+  // power of two in [4, kDiagMax]; tests reach the overflow route with few reasons), the table (overflow
+  // word, keys, counts) and the pinned block it and the pod's summary cross in
+  uint32_t diag_slots = kDiagMax;
+  DBuf<uint8_t> dg_tab;
+  uint8_t* dg_host = nullptr;
   DBuf<int32_t> knorm;    // normalized scores of one kept pod
   DBuf<uint8_t> vblk;     // device cycle view block (Engine::view)
   bool vblk_fresh = true;
@@ -5683,6 +5690,7 @@ Engine::~Engine() {
   if (p_->apstage) (void)hipHostFree(p_->apstage);
   if (p_->vstage) (void)hipHostFree(p_->vstage);
   if (p_->rk_host) (void)hipHostFree(p_->rk_host);
+  if (p_->dg_host) (void)hipHostFree(p_->dg_host);
   if (p_->apstage_ev) (void)hipEventDestroy(p_->apstage_ev);
   if (p_->ev0) (void)hipEventDestroy(p_->ev0);
   if (p_->ev1) (void)hipEventDestroy(p_->ev1);
@@ -5706,6 +5714,10 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
   if (env_long("KSG_RANK_TILE", &v)) {  // the largest power of two <= the value, within [128, kRankTile]
     I.rank_tile = 128;
     while (I.rank_tile < kRankTile && 2ul * I.rank_tile <= (unsigned long)v) I.rank_tile *= 2;
+  }
+  if (env_long("KSG_DIAG_SLOTS", &v)) {  // the largest power of two <= the value, within [4, kDiagMax]
+    I.diag_slots = 4;
+    while (I.diag_slots < kDiagMax && 2ul * I.diag_slots <= (unsigned long)v) I.diag_slots *= 2;
   }
   if (env_long("KSG_RUN", &v)) I.run_on = (int)v;
   if (env_long("KSG_RUN_MIN", &v)) I.run_min = std::max<uint32_t>(1, (uint32_t)v);
@@ -8532,3 +8544,4 @@ extern "C" int ksg_debug_arith(int op, const int64_t* in, uint32_t cols, int64_t
 }
 
 #include "ranked.hip"
+#include "diagnosis.hip"

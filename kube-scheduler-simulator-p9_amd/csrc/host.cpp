@@ -4374,6 +4374,20 @@ struct Cluster {
     }
     return "";
   }
+  // The reasons of that status (Status.Reasons(): what FitError.Error() counts):
+  // NodeResourcesFit and VolumeBinding append one reason per shortfall / conflict,
+  // which filter_message joins with ", "; every other plugin has its one message.
+  vector<string> filter_reasons(int pos, uint32_t detail) const {
+    const string m = filter_message(pos, detail);
+    if (plugins[pos] != P_FIT && !(is_volume(plugins[pos]) && vkind[pos] == VK_BIND)) return {m};
+    vector<string> out;
+    for (size_t a = 0; a <= m.size();) {
+      const size_t b = std::min(m.find(", ", a), m.size());
+      out.push_back(m.substr(a, b - a));
+      a = b + 2;
+    }
+    return out;
+  }
 
   // ------------------------------------------------------------ per-plugin statuses
   // What each wrapped plugin's extension point returns for the cycle of queue pod
@@ -4471,6 +4485,61 @@ struct Cluster {
       case P_PORTS: return C_UNSCHED;
       default: return C_UNRESOLVABLE;  // TaintToleration, NodeAffinity, NodeUnschedulable, NodeName
     }
+  }
+  // ---- unschedulable diagnosis (ksg_filter_histogram / ksg_fit_error; diag_call below)
+  uint64_t diag_routes[2] = {0, 0};  // diagnostic: calls answered from the device table / by the host count
+  // The host count of kept pod q's filter row (the device table overflowed): the
+  // per-node calls' answers, as the cycle view's overflow branch
+  bool diag_host_counts(uint32_t q, vector<ksg::Engine::DiagEntry>& out) {
+    const PodOutputs* o = outputs_of(q);
+    if (!o) return false;
+    map<std::pair<uint32_t, int32_t>, uint32_t> cnt;
+    const uint32_t N = hi - lo;
+    for (uint32_t i = 0; i < N; ++i) {
+      const uint32_t code = o->filter[i];
+      int32_t st = 0;
+      if (code == KSG_FILTER_NOT_EVALUATED) st = -1;
+      else if (code != KSG_FILTER_PASS) st = filter_fail_code(q, code_pos(code), i, code_detail(code));
+      cnt[{code, st}]++;
+    }
+    out.clear();
+    for (auto& kv : cnt) out.push_back({kv.first.first, kv.first.second, kv.second});
+    return true;
+  }
+  // upstream v1.30.4 framework.FitError.Error() without its PostFilter clause, for
+  // kept pod q with summary S and (code, status, count) entries e (include/ksg.h)
+  string fit_error_text(uint32_t q, const ksg_pod_summary& S, const vector<ksg::Engine::DiagEntry>& e) const {
+    if (S.status != 1) return "";
+    const PodMeta& m = meta[q];
+    string s = "0/" + std::to_string(nodes.size()) + " nodes are available:";
+    if (m.prefilter_fail_pos >= 0) {  // the PreFilter status's message alone
+      string msg = m.prefilter_fail_msg;
+      if (m.merge_reject) {  // framework.go RunPreFilterPlugins: the plugins that returned a node set
+        vector<string> with;
+        for (int pos = 0; pos <= m.prefilter_fail_pos && pos < n_plugins; ++pos)
+          if ((plugins[pos] == P_NA && m.restricted) || (vkind[pos] == VK_BIND && m.vb_restricted))
+            with.push_back(names[pos]);
+        if (with.size() == 1) {
+          msg = "node(s) didn't satisfy plugin " + with[0];
+        } else {
+          msg = "node(s) didn't satisfy plugin(s) [";
+          for (size_t i = 0; i < with.size(); ++i) msg += (i ? " " : "") + with[i];
+          msg += "] simultaneously";
+        }
+      }
+      return s + " " + msg + ".";
+    }
+    map<string, uint64_t> reasons;
+    for (auto& x : e) {
+      if (x.code == KSG_FILTER_PASS || x.code == KSG_FILTER_NOT_EVALUATED) continue;
+      for (auto& r : filter_reasons(code_pos(x.code), code_detail(x.code))) reasons[r] += x.count;
+    }
+    vector<string> parts;
+    for (auto& kv : reasons) parts.push_back(std::to_string(kv.second) + " " + kv.first);
+    std::sort(parts.begin(), parts.end());  // (sort.Strings: byte order)
+    for (size_t i = 0; i < parts.size(); ++i) s += (i ? ", " : " ") + parts[i];
+    if (!parts.empty()) s += ".";
+    return s;
   }
   // The same rule per profile position, for the device view (Engine::view)
   ksg::Engine::ViewCfg vcfg_;
@@ -5596,4 +5665,60 @@ int kept_pod_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
   const int rc = fn(*c.eng, q, user, c.err);
   return rc == KSG_OK ? KSG_OK : ctx->fail(c.err, rc);
 }
+
+// The same for the unschedulable diagnosis (ksg_filter_histogram / ksg_fit_error,
+// csrc/diagnosis.hip), whose answer also needs the object model: count is the
+// engine's device pass over q's kept filter row; when its table overflowed the
+// row is counted here, from the kept outputs; then the order, the positions and
+// (text) the messages, all under the one lock.
+int diag_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
+              int (*count)(Engine& eng, uint32_t prog, const Engine::ViewCfg& cfg, Engine::DiagCounts& out,
+                           std::string& err),
+              const DiagRequest& rq) {
+  KSG_LOCK(ctx);
+  KSG_GUARD(ctx);
+  auto& c = ctx->c;
+  if (c.shards > 1) return ctx->fail(std::string(what) + ": not offered on a sharded context", KSG_E_INVALID);
+  if (!args_ok || q >= c.queue.size() || q >= c.meta.size()) return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
+  Engine::DiagCounts dc;
+  const int rc = count(*c.eng, q, c.view_cfg(), dc, c.err);
+  if (rc != KSG_OK) return ctx->fail(c.err, rc);
+  if (dc.overflow && !c.diag_host_counts(q, dc.entries)) return ctx->fail(c.err, KSG_E_STATE);
+  c.diag_routes[dc.overflow ? 1 : 0]++;
+  if (rq.text) {
+    const std::string s = c.fit_error_text(q, dc.summary, dc.entries);
+    *rq.len = s.size();
+    if (s.empty()) return KSG_OK;
+    if (!rq.buf || rq.bcap < s.size()) return KSG_E_NOBUF;
+    std::memcpy(rq.buf, s.data(), s.size());
+    return KSG_OK;
+  }
+  // the codes as ksg_filter_codes reports them (device position -> profile position), in order
+  std::map<std::pair<uint32_t, int32_t>, ksg_filter_bucket> buckets;
+  for (const Engine::DiagEntry& e : dc.entries) {
+    ksg_filter_bucket b{e.code, -1, e.status, 0};
+    if (e.code == KSG_FILTER_PASS) b.pos = c.n_plugins;
+    else if (e.code != KSG_FILTER_NOT_EVALUATED) {
+      b.pos = c.code_pos(e.code);
+      b.code = ((uint32_t)b.pos << 24) | c.code_detail(e.code);
+    }
+    auto it = buckets.emplace(std::make_pair(b.code, b.status), b).first;
+    it->second.count += e.count;
+  }
+  *rq.n_out = (uint32_t)buckets.size();
+  if (rq.cap < buckets.size()) return KSG_E_NOBUF;
+  size_t i = 0;
+  for (auto& kv : buckets) rq.out[i++] = kv.second;
+  return KSG_OK;
+}
 }  // namespace ksg
+
+// diagnostic (not in ksg.h): out[2] = diagnosis calls (ksg_filter_histogram / ksg_fit_error)
+// answered from the device table so far, and by the host count of the kept filter row
+extern "C" int ksg_debug_diag_routes(ksg_ctx* ctx, uint64_t* out) {
+  KSG_LOCK(ctx);
+  if (!ctx || !out) return KSG_E_INVALID;
+  out[0] = ctx->c.diag_routes[0];
+  out[1] = ctx->c.diag_routes[1];
+  return KSG_OK;
+}

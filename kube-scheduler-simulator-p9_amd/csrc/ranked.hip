@@ -1,6 +1,6 @@
 // Ranked candidates (ksg_ranked_nodes, include/ksg.h): the K best feasible nodes
 // of a kept pod's cycle in the engine's own selection order, selected on the
-// device.  Part of the engine's translation unit (engine.hip includes it last).
+// device.  Part of the engine's translation unit (engine.hip includes it at its end).
 //
 //   k_rank_keys   one block per tile of nodes: every node's selection key from
 //                 the pod's kept filter row, raw score rows and summary (the

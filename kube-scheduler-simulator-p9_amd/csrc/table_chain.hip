@@ -2406,6 +2406,37 @@ __device__ __forceinline__ uint32_t view_slot(unsigned long long* tab, uint32_t 
   if (htab) htab[kViewSlots] = (unsigned long long)gen << 32;
   return kViewSlots;
 }
+// The Filter outcome of node n from its device filter code (the view's per-node
+// arrays, and the failure histogram of diagnosis.hip): fp the failing profile
+// position (n_profile: passed every filter; -1: not evaluated), fc the
+// framework.Code of that failure (0: none).  True when the node failed a filter.
+__device__ __forceinline__ bool view_fail(const DevCluster& C, const ksg_prog* h, const ViewDev& V, uint32_t code,
+                                          uint32_t n, int& fp, int& fc) {
+  fp = -1;
+  fc = 0;
+  if (code == KSG_FILTER_PASS) {
+    fp = V.n_profile;
+    return false;
+  }
+  if (code == KSG_FILTER_NOT_EVALUATED) return false;
+  const uint32_t d = code >> 24;
+  const bool vol = V.dev_vol[d] != 0;
+  fp = V.prof_of_dev[d] + (vol ? (int)((code >> 16) & 0xFFu) : 0);
+  const uint32_t detail = vol ? code & 0xFFFFu : code & 0xFFFFFFu;
+  switch (V.kind[fp]) {
+    case kVkUnsched: fc = 2; break;
+    case kVkFit:
+      fc = 2;
+      for (uint32_t r = 0; r < C.R && r < KSG_MAX_RES; ++r)
+        if ((detail >> (1 + r)) & 1u)
+          if (h->req[r] > C.alloc[(size_t)r * C.N + n]) fc = 3;
+      break;
+    case kVkPts: fc = detail == KSG_PTS_MISSING_LABEL ? 3 : 2; break;
+    case kVkIpa: fc = detail == KSG_IPA_AFFINITY ? 3 : 2; break;
+    default: fc = 3;
+  }
+  return true;
+}
 // out: the device block (slot table, summary); hout: where the per-node arrays go —
 // the host's pinned block itself (written over the link by this kernel, no copy
 // launch after it) or out.
@@ -2419,29 +2450,8 @@ __device__ __forceinline__ void view_body(const DevCluster& C, const DevProfile&
   const ProgView PV = view(prog);
   const ksg_prog* h = PV.h;
   const uint32_t code = act ? filter[n] : KSG_FILTER_NOT_EVALUATED;
-  int fp = -1, fc = 0;
-  bool need = false;
-  if (code == KSG_FILTER_PASS) {
-    fp = V.n_profile;
-  } else if (code != KSG_FILTER_NOT_EVALUATED) {
-    const uint32_t d = code >> 24;
-    const bool vol = V.dev_vol[d] != 0;
-    fp = V.prof_of_dev[d] + (vol ? (int)((code >> 16) & 0xFFu) : 0);
-    const uint32_t detail = vol ? code & 0xFFFFu : code & 0xFFFFFFu;
-    switch (V.kind[fp]) {
-      case kVkUnsched: fc = 2; break;
-      case kVkFit:
-        fc = 2;
-        for (uint32_t r = 0; r < C.R && r < KSG_MAX_RES; ++r)
-          if ((detail >> (1 + r)) & 1u)
-            if (h->req[r] > C.alloc[(size_t)r * C.N + n]) fc = 3;
-        break;
-      case kVkPts: fc = detail == KSG_PTS_MISSING_LABEL ? 3 : 2; break;
-      case kVkIpa: fc = detail == KSG_IPA_AFFINITY ? 3 : 2; break;
-      default: fc = 3;
-    }
-    need = true;
-  }
+  int fp, fc;
+  bool need = view_fail(C, h, V, code, n, fp, fc);
   // message slots: one insert per distinct code of the wave
   unsigned long long* tab = reinterpret_cast<unsigned long long*>(out);
   if (n == 0 && hout == out && sum) *reinterpret_cast<ksg_pod_summary*>(out + V.off_sum) = *sum;

@@ -31,6 +31,14 @@ class _RankedNode(ctypes.Structure):
     _fields_ = [("node", ctypes.c_int32), ("total", ctypes.c_int32)]
 
 
+DIAG_MAX = 1024  # KSG_DIAG_MAX
+
+
+class _FilterBucket(ctypes.Structure):
+    _fields_ = [("code", ctypes.c_uint32), ("pos", ctypes.c_int32), ("status", ctypes.c_int32),
+                ("count", ctypes.c_uint32)]
+
+
 class _Opts(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("stream", ctypes.c_void_p), ("shard_rank", ctypes.c_uint32),
                 ("shard_count", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
@@ -178,7 +186,7 @@ def load_library():
     L.ksg_prescore_status.argtypes = [vp, u32, u32, ctypes.POINTER(i32), cp, sz, ctypes.POINTER(sz)]
     L.ksg_normalized_scores.argtypes = [vp, u32, u32, ctypes.POINTER(i64), u32]
     L.ksg_ranked_nodes.argtypes = [vp, u32, u32, ctypes.POINTER(_RankedNode), ctypes.POINTER(u32)]
-    L.ksg_cycle_view_acquire.argtypes = [vp, u32, ctypes.POINTER(ctypes.POINTER(_CycleView))]
+    L.ksg_cycle_view_acquire.argtypes =[vp, u32, ctypes.POINTER(ctypes.POINTER(_CycleView))]
     L.ksg_cycle_view_release.argtypes = [ctypes.POINTER(_CycleView)]
     L.ksg_cycle_view_release.restype = None
     L.ksg_debug_path_counts.argtypes = [vp, ctypes.c_void_p]
@@ -503,6 +511,47 @@ class Scheduler:
         n = ctypes.c_uint32()
         self._chk(self.L.ksg_ranked_nodes(self.h, q, k, arr, ctypes.byref(n)), "ksg_ranked_nodes")
         return [(arr[i].node, arr[i].total) for i in range(n.value)]
+
+    def filter_histogram(self, q):
+        """ksg_filter_histogram: [(code, pos, status, count)] over every local node of kept pod
+        q's cycle, one entry per distinct (filter code, framework status), ascending; the
+        counts sum to the node count."""
+        # (bound on first use, like the diagnostics: KSG_LIB may name an A/B build from before the call)
+        self.L.ksg_filter_histogram.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(_FilterBucket),
+                                                ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        n = ctypes.c_uint32()
+        cap = 64
+        while True:
+            arr = (_FilterBucket * cap)()
+            rc = self.L.ksg_filter_histogram(self.h, q, arr, cap, ctypes.byref(n))
+            if rc != -5:  # KSG_E_NOBUF: n holds the needed count
+                break
+            cap = n.value
+        self._chk(rc, "ksg_filter_histogram")
+        return [(b.code, b.pos, b.status, b.count) for b in arr[:n.value]]
+
+    def fit_error(self, q) -> str:
+        """ksg_fit_error: upstream's FitError.Error() text for an unschedulable kept pod q
+        ("0/N nodes are available: ..."), "" for a scheduled pod or a cycle that ended in an error."""
+        self.L.ksg_fit_error.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t,
+                                         ctypes.POINTER(ctypes.c_size_t)]
+        n = ctypes.c_size_t()
+        cap = 4096  # (most sentences fit: one call; KSG_E_NOBUF leaves the size in n)
+        while True:
+            buf = ctypes.create_string_buffer(cap)
+            rc = self.L.ksg_fit_error(self.h, q, buf, cap, ctypes.byref(n))
+            if rc != -5:
+                break
+            cap = n.value
+        self._chk(rc, "ksg_fit_error")
+        return buf.raw[:n.value].decode()
+
+    def diag_routes(self):
+        """Diagnostic: (diagnosis calls answered from the device table, by the host count) so far."""
+        out = (ctypes.c_uint64 * 2)()
+        self.L.ksg_debug_diag_routes.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._chk(self.L.ksg_debug_diag_routes(self.h, out), "ksg_debug_diag_routes")
+        return out[0], out[1]
 
     def node_nonzero(self):
         """NonZeroRequested (cpu milli, memory bytes) rows of every local node."""
