@@ -50,7 +50,8 @@ extern "C" {
  * narrow as their values allow (score_bytes / normalized_bytes; ksg_view_score).
  * Added within 4 (no existing entry point or struct changed): ksg_ranked_nodes,
  * ksg_ranked_node, KSG_RANK_MAX; ksg_filter_histogram, ksg_fit_error,
- * ksg_filter_bucket, KSG_DIAG_MAX. */
+ * ksg_filter_bucket, KSG_DIAG_MAX; ksg_headroom (the call and the struct),
+ * ksg_headroom_nodes, ksg_resource_name, KSG_HEADROOM_BOUNDS. */
 #define KSG_ABI_VERSION 4
 
 #define KSG_OK 0
@@ -348,6 +349,63 @@ typedef struct ksg_filter_bucket {
 } ksg_filter_bucket;
 int ksg_filter_histogram(ksg_ctx* ctx, uint32_t q, ksg_filter_bucket* out, uint32_t cap, uint32_t* n_out);
 int ksg_fit_error(ksg_ctx* ctx, uint32_t q, char* buf, size_t cap, size_t* len);
+/* Headroom: how many more copies of queue pod q fit, on which nodes, and which
+ * constraint runs out first -- the cluster-capacity question, counted on the device
+ * in one pass over the node columns per pod.
+ * The per-node count of pod q on local node n, against the device snapshot as it
+ * stands when the call runs (every assume, Reserve and event applied so far; the
+ * call is ordered on the context stream after any pending delta):
+ *   0 when the pod's PreFilter rejected it or ended in an error, when n is outside
+ *   its PreFilterResult, or when one of the profile's TaintToleration, NodeAffinity,
+ *   NodeUnschedulable or NodeName Filters fails on n (the node is not "open");
+ *   otherwise min(room, min over the resource columns r with request[r] > 0 of
+ *   fit_r), where room = max(0, allowed pods - pod count), free_r = allocatable_r -
+ *   requested_r and fit_r = free_r < 0 ? 0 : floor(free_r / request[r]).  A pod whose
+ *   requests are all zero is bounded by the room alone, as fitsRequest returns early.
+ * This is the number of further copies of q upstream's fitsRequest admits one after
+ * another on n: k copies add k x request to requested and k to the pod count.  It is
+ * at most room, so it fits int32.  Integer arithmetic throughout; exact.
+ * ksg_headroom fills out[i] for queue pods [first, first + count) in one launch:
+ *   replicas    the sum of the per-node counts over the local nodes
+ *   nodes       nodes whose count is >= 1
+ *   open_nodes  nodes that pass every Filter plugin other than NodeResourcesFit
+ *   max_node    the largest per-node count (0 when replicas == 0)
+ *   best_node   the lowest global node index holding max_node (-1 when replicas == 0)
+ *   bound[]     over the open nodes, count 0 included (what the cluster is short of):
+ *               which constraint is the minimum -- index 0 the pod room, index 1 + r
+ *               resource column r (the bit order of the Fit filter's detail;
+ *               ksg_resource_name names r); a tie counts for the lowest index;
+ *               sum(bound) == open_nodes.
+ * ksg_headroom_nodes writes the per-node counts of one pod: n must be the local node
+ * count (the convention of ksg_filter_codes).
+ * ksg_resource_name: the name of resource column r ("cpu", "memory",
+ * "ephemeral-storage", then the scalar resources in vocabulary order): the rows of
+ * ksg_node_requested and bound[1 + r].  Buffer convention of ksg_annotations;
+ * KSG_E_RANGE past the last column.
+ * Profiles: NodeResourcesFit must be there, and every plugin with a Filter must be
+ * one of NodeResourcesFit, TaintToleration, NodeAffinity, NodeUnschedulable,
+ * NodeName (plugins that only score or only run PostFilter do not matter).  With
+ * PodTopologySpread, InterPodAffinity, NodePorts or a volume plugin replicas of a
+ * pod interact through that plugin's Filter and no closed form exists:
+ * KSG_E_INVALID, the message naming the plugin.  A sharded context: KSG_E_INVALID.
+ * out NULL, the range outside the queue, n different from the local node count:
+ * KSG_E_RANGE.  count == 0: KSG_OK, nothing written.  The calls need no kept
+ * outputs and no earlier cycle of the pod, change no scheduling state, and two
+ * calls return the same bytes.
+ * (C: the struct is named by its tag, `struct ksg_headroom`, beside the call of the
+ * same name -- as stat(2).) */
+#define KSG_HEADROOM_BOUNDS 9            /* 1 + KSG_MAX_RES */
+struct ksg_headroom {
+  int64_t  replicas;    /* sum over local nodes of the per-node count */
+  int32_t  nodes;       /* nodes whose count is >= 1 */
+  int32_t  open_nodes;  /* nodes that pass every Filter plugin other than NodeResourcesFit */
+  int32_t  max_node;    /* the largest per-node count (0 when replicas == 0) */
+  int32_t  best_node;   /* lowest global node index holding max_node; -1 when replicas == 0 */
+  uint32_t bound[KSG_HEADROOM_BOUNDS]; /* over the open nodes: which constraint is the minimum */
+};
+int ksg_headroom(ksg_ctx* ctx, uint32_t first, uint32_t count, struct ksg_headroom* out);
+int ksg_headroom_nodes(ksg_ctx* ctx, uint32_t q, int32_t* out, uint32_t n);
+int ksg_resource_name(const ksg_ctx* ctx, uint32_t r, char* buf, size_t cap, size_t* len);
 /* PostFilter (wrappedplugin.go:550-577 -> store.go:442 AddPostFilterResult):
  * DefaultPreemption's dry run for an unschedulable pod q (PodEligibleToPreemptOthers,
  * nodesWherePreemptionMightHelp, SelectVictimsOnNode, pickOneNodeForPreemption of

@@ -432,6 +432,20 @@ __device__ __forceinline__ int64_t div_small(int64_t x, int64_t a) {
   else if ((q + 1) * a <= x) q++;
   return q;
 }
+// min(floor(x / a), cap) for 0 <= x < 2^63, 1 <= a < 2^63, 0 <= cap < 2^31 -- exact
+// (headroom.hip: how many requests of a fit into x, clipped to the running minimum).
+// Gates: (1) the clip answers first: x >= cap * a gives cap, with the product
+// formed in 128 bits (a high half that is not zero means cap * a >= 2^64 > x, so
+// the quotient is below cap); cap = 0 always ends here.  (2) Otherwise the
+// quotient is below cap < 2^31 and div_small gives it: the 32-bit divide for
+// 32-bit operands, else the f64 reciprocal estimate with its exact correction
+// for x < 2^52 and an estimate below 2^20, else the 64-bit divide -- its own gates,
+// nothing restated here.
+__device__ __forceinline__ int64_t div_cap(int64_t x, int64_t a, int32_t cap) {
+  const uint64_t lo = (uint64_t)(uint32_t)cap * (uint64_t)a, hi = __umul64hi((uint64_t)(uint32_t)cap, (uint64_t)a);
+  if (hi == 0 && (uint64_t)x >= lo) return cap;
+  return div_small(x, a);
+}
 __device__ __forceinline__ int64_t least_req(int64_t a, int64_t q) {  // leastRequestedScore
   return q > a ? 0 : div_small((a - q) * 100, a);
 }
@@ -2767,7 +2781,8 @@ enum : int {
   KSG_ARITH_BA = 6,           // (q, a) x cols / 2 -> the BalancedAllocation score
   KSG_ARITH_GO_LOG = 7,       // bits -> bits of go_log
   KSG_ARITH_IPA_NORM = 8,     // s, mn, mx -> ipa_norm
-  KSG_ARITH_OPS = 9
+  KSG_ARITH_DIV_CAP = 9,      // x, a, cap -> div_cap
+  KSG_ARITH_OPS = 10
 };
 // Self-test of the lane exchanges against ds_bpermute shuffles (diagnostic ABI).
 __global__ void k_selftest_lanes(const uint64_t* in, int32_t* bad) {
@@ -2841,6 +2856,7 @@ __global__ __launch_bounds__(256) void k_selftest_arith(int op, const int64_t* _
     case KSG_ARITH_BA: r = ba_walk(PairSrc{in, n, i, cols}); break;
     case KSG_ARITH_GO_LOG: r = d2bits(go_log(__longlong_as_double(x))); break;
     case KSG_ARITH_IPA_NORM: r = ipa_norm(x, y, z); break;
+    case KSG_ARITH_DIV_CAP: r = div_cap(x, y, (int32_t)z); break;
     default: break;
   }
   out[i] = r;
@@ -5540,6 +5556,10 @@ struct Engine::Impl {
   uint32_t diag_slots = kDiagMax;
   DBuf<uint8_t> dg_tab;
   uint8_t* dg_host = nullptr;
+  // headroom (headroom.hip): the device result structs (or one pod's node row) and the pinned block they cross in
+  DBuf<uint8_t> hr_dev;
+  uint8_t* hr_host = nullptr;
+  size_t hr_host_bytes = 0;
   DBuf<int32_t> knorm;    // normalized scores of one kept pod
   DBuf<uint8_t> vblk;     // device cycle view block (Engine::view)
   bool vblk_fresh = true;
@@ -5691,6 +5711,7 @@ Engine::~Engine() {
   if (p_->vstage) (void)hipHostFree(p_->vstage);
   if (p_->rk_host) (void)hipHostFree(p_->rk_host);
   if (p_->dg_host) (void)hipHostFree(p_->dg_host);
+  if (p_->hr_host) (void)hipHostFree(p_->hr_host);
   if (p_->apstage_ev) (void)hipEventDestroy(p_->apstage_ev);
   if (p_->ev0) (void)hipEventDestroy(p_->ev0);
   if (p_->ev1) (void)hipEventDestroy(p_->ev1);
@@ -8545,3 +8566,4 @@ extern "C" int ksg_debug_arith(int op, const int64_t* in, uint32_t cols, int64_t
 
 #include "ranked.hip"
 #include "diagnosis.hip"
+#include "headroom.hip"

@@ -1,0 +1,274 @@
+// Headroom (ksg_headroom / ksg_headroom_nodes, include/ksg.h): how many more
+// copies of a queue pod fit on every node of the device snapshot, counted on the
+// device.  Part of the engine's translation unit (engine.hip includes it after
+// diagnosis.hip).
+//
+//   k_headroom<false>  a (node tile x pod tile) grid, as the what-if pass.  A block
+//                 of 256 threads owns kHrTile = 256 x kHrNpt nodes: every thread
+//                 loads its nodes' rows once, as free_r = allocatable_r -
+//                 requested_r for the R resource columns and room = max(0,
+//                 allowed - podcnt), and keeps them in registers.  It then walks
+//                 the kHrPods pods of its pod tile over them; the pods' program
+//                 headers and requests are wave-uniform reads through the scalar
+//                 cache.  The static filters are node_filter<kPmHeadroom>, the
+//                 switch every kernel shares (their per-node operands -- taints,
+//                 labels, the node flags -- are read there, from L1/L2 after the
+//                 tile's first pod); the reject flags and the PreFilterResult
+//                 bitmask as k_eval reads them.  The count is a running minimum:
+//                 it starts at the room and every requested column r lowers it to
+//                 div_cap(free_r, req_r, count), so the constraint that lowered it
+//                 last is the lowest index holding the minimum (bound[]).
+//   k_headroom<true>   the same body for one pod with a store per node instead of
+//                 the reduction (ksg_headroom_nodes).
+//
+// Accumulation, all integer: per wave the node counts and bound[] are ballots
+// and popcounts, the replica sum and the (count, node) key DPP reductions of
+// 32-bit words (the form of wave_max_u64; no 64-bit shuffle); lane 0 adds the
+// wave's values to the block's LDS copy of the pod tile's result structs; after
+// the last pod the block adds every non-zero LDS word to the device structs,
+// one global atomic per block and field.  max_node / best_node travel as one
+// 64-bit key, (count << 32) | (0xFFFFFFFF - global node), under an atomic max
+// in the place of the two fields; the host decodes it.  The answer does not
+// depend on the order in which waves and blocks arrive.
+//
+// Forward progress: no thread waits on another thread's progress (the one
+// barrier is reached by every thread of the block: the pod and node loops hold
+// no return), and every loop is bounded by a tile constant, the profile length
+// or KSG_MAX_RES.
+//
+// kHrTile = 1024 nodes and kHrPods = 32 pods: several node blocks per pod from
+// 1025 nodes, several pod tiles from 33 pods, so no override is read.
+#include "../../include/ksg.h"
+
+struct ksg_ctx;
+
+namespace ksg {
+
+using Headroom = struct ::ksg_headroom;  // (the function of the same name hides the struct's)
+constexpr uint32_t kHrNpt = 4;              // nodes per thread
+constexpr uint32_t kHrTile = 256 * kHrNpt;  // nodes per block
+constexpr uint32_t kHrPods = 32;            // pods per block (grid.y tiles)
+constexpr uint32_t kHrWords = sizeof(Headroom) / 4;
+constexpr uint32_t kPmHeadroom = (1u << KP_TAINT) | (1u << KP_NA) | (1u << KP_UNSCHED) | (1u << KP_NODENAME);
+static_assert(KSG_HEADROOM_BOUNDS == 1 + KSG_MAX_RES, "bound[]: the pod room, then every resource column");
+static_assert(sizeof(Headroom) == 64 && offsetof(Headroom, nodes) == 8 && offsetof(Headroom, open_nodes) == 12 &&
+                  offsetof(Headroom, max_node) == 16 && offsetof(Headroom, best_node) == 20 &&
+                  offsetof(Headroom, bound) == 24,
+              "the kernel accumulates into the struct's own layout; the key lies over max_node / best_node");
+// 32-bit words of a struct ksg_headroom
+enum : uint32_t { kHrwReplicas = 0, kHrwNodes = 2, kHrwOpen = 3, kHrwKey = 4, kHrwBound = 6 };
+
+// The sum of a non-negative 64-bit value below 2^40 over the wave's active lanes,
+// as two 32-bit DPP sums (64 x 2^20 fits either; wave_max_u64's note on 64-bit shuffles)
+__device__ __forceinline__ uint64_t wave_sum_u40(uint64_t v) {
+  const uint32_t lo = (uint32_t)__ockl_wfred_add_i32((int32_t)(v & 0xFFFFFu));
+  const uint32_t hi = (uint32_t)__ockl_wfred_add_i32((int32_t)(v >> 20));
+  return ((uint64_t)hi << 20) + lo;
+}
+
+template <bool PER_NODE>
+__global__ __launch_bounds__(256) void k_headroom(DevCluster C, DevProfile F, const uint8_t* __restrict__ progs,
+                                                  const uint64_t* __restrict__ prog_off, uint32_t q0, uint32_t count,
+                                                  Headroom* out, int32_t* out_nodes) {
+  __shared__ __attribute__((aligned(16))) uint32_t acc[PER_NODE ? 1 : kHrPods * kHrWords];  // (64-bit words inside)
+  if (!PER_NODE) {
+    for (uint32_t t = threadIdx.x; t < kHrPods * kHrWords; t += 256) acc[t] = 0;
+    __syncthreads();
+  }
+  // the block's node rows, once
+  const uint32_t base = blockIdx.x * kHrTile + threadIdx.x;
+  int64_t fr[kHrNpt][KSG_MAX_RES];
+  int32_t room[kHrNpt];
+#pragma unroll
+  for (uint32_t k = 0; k < kHrNpt; ++k) {
+    const uint32_t n = base + k * 256;
+    const bool live = n < C.N;
+    const int32_t left = live ? C.allowed[n] - C.podcnt[n] : 0;
+    room[k] = left > 0 ? left : 0;
+#pragma unroll
+    for (uint32_t r = 0; r < KSG_MAX_RES; ++r)
+      fr[k][r] = (live && r < C.R) ? C.alloc[(size_t)r * C.N + n] - C.req[(size_t)r * C.N + n] : 0;
+  }
+#pragma unroll 1
+  for (uint32_t pi = 0; pi < kHrPods; ++pi) {
+    const uint32_t j = blockIdx.y * kHrPods + pi;
+    if (j >= count) break;  // (block-uniform)
+    const ProgView V = view(progs + prog_off[q0 + j]);
+    const ksg_prog* h = V.h;
+    const uint32_t flags = h->flags;
+    const bool rejected = (flags & (KPF_PREFILTER_REJECT | KPF_PREFILTER_ERROR)) != 0;
+    bool open[kHrNpt];
+    int32_t cnt[kHrNpt];
+    uint32_t which[kHrNpt];
+#pragma unroll
+    for (uint32_t k = 0; k < kHrNpt; ++k) {
+      const uint32_t n = base + k * 256;
+      bool ok = n < C.N && !rejected &&
+                !((flags & KPF_RESTRICT) && !bit(V.u32 + h->restrict_off, h->restrict_words, (int32_t)n));
+      if (ok) {
+        uint32_t code = KSG_FILTER_PASS;
+#pragma unroll 1
+        for (int pos = 0; pos < F.n && code == KSG_FILTER_PASS; ++pos)
+          code = node_filter<kPmHeadroom>(F.plugins[pos], pos, C, V, n);
+        ok = code == KSG_FILTER_PASS;
+      }
+      open[k] = ok;
+      cnt[k] = ok ? room[k] : 0;
+      which[k] = 0;
+    }
+    if (!(flags & KPF_ZERO_REQUEST)) {  // (fit_filter: no resource is looked at for a zero-request pod)
+#pragma unroll
+      for (uint32_t r = 0; r < KSG_MAX_RES; ++r) {
+        const int64_t rq = h->req[r];
+        if (r >= C.R || rq <= 0) continue;  // (wave-uniform)
+#pragma unroll
+        for (uint32_t k = 0; k < kHrNpt; ++k) {
+          if (!open[k]) continue;
+          const int64_t f = fr[k][r];
+          const int32_t fit = f < 0 ? 0 : (int32_t)div_cap(f, rq, cnt[k]);
+          if (fit < cnt[k]) {  // (a tie keeps the lower index)
+            cnt[k] = fit;
+            which[k] = 1 + r;
+          }
+        }
+      }
+    }
+    if (PER_NODE) {
+#pragma unroll
+      for (uint32_t k = 0; k < kHrNpt; ++k) {
+        const uint32_t n = base + k * 256;
+        if (n < C.N) out_nodes[n] = cnt[k];
+      }
+      continue;
+    }
+    // the wave's share of pod j, then lane 0 into the block's struct
+    uint64_t sum = 0, key = 0;
+    uint32_t n_pos = 0, n_open = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kHrNpt; ++k) {
+      sum += (uint32_t)cnt[k];
+      const uint64_t kk = ((uint64_t)(uint32_t)cnt[k] << 32) | (0xFFFFFFFFu - (C.goff + base + k * 256));
+      if (cnt[k] > 0 && kk > key) key = kk;
+      n_pos += (uint32_t)__popcll(__ballot(cnt[k] > 0));
+      n_open += (uint32_t)__popcll(__ballot(open[k]));
+    }
+    if (n_open == 0) continue;  // (wave-uniform: nothing of this wave counts for the pod)
+    const uint64_t wsum = wave_sum_u40(sum);
+    const uint64_t wkey = wave_max_u64(key);
+    uint32_t* a = acc + pi * kHrWords;
+    if (lane0()) {
+      atomicAdd(a + kHrwOpen, n_open);
+      if (n_pos) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(a + kHrwReplicas), (unsigned long long)wsum);
+        atomicAdd(a + kHrwNodes, n_pos);
+        atomicMax(reinterpret_cast<unsigned long long*>(a + kHrwKey), (unsigned long long)wkey);
+      }
+    }
+    for (uint32_t i = 0; i < 1 + C.R; ++i) {  // (R <= KSG_MAX_RES: the columns the cluster has)
+      uint32_t c = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < kHrNpt; ++k) c += (uint32_t)__popcll(__ballot(open[k] && which[k] == i));
+      if (c && lane0()) atomicAdd(a + kHrwBound + i, c);
+    }
+  }
+  if (PER_NODE) return;
+  __syncthreads();
+  // one global atomic per block and non-zero field
+  const uint32_t pods = count - blockIdx.y * kHrPods < kHrPods ? count - blockIdx.y * kHrPods : kHrPods;
+  for (uint32_t t = threadIdx.x; t < pods * kHrWords; t += 256) {
+    const uint32_t pi = t / kHrWords, w = t % kHrWords;
+    uint32_t* g = reinterpret_cast<uint32_t*>(out + (size_t)blockIdx.y * kHrPods + pi) + w;
+    const uint32_t* a = acc + pi * kHrWords + w;
+    if (w == kHrwReplicas || w == kHrwKey) {
+      const unsigned long long v = *reinterpret_cast<const unsigned long long*>(a);
+      if (!v) continue;
+      if (w == kHrwReplicas) atomicAdd(reinterpret_cast<unsigned long long*>(g), v);
+      else atomicMax(reinterpret_cast<unsigned long long*>(g), v);
+    } else if (w == kHrwNodes || w == kHrwOpen || (w >= kHrwBound && w < kHrwBound + KSG_HEADROOM_BOUNDS)) {
+      if (*a) atomicAdd(g, *a);
+    }
+  }
+}
+
+namespace {
+// one launch covers at most this many pods (grid.y <= 65535)
+constexpr uint32_t kHrLaunchPods = 65535u * kHrPods;
+
+struct HeadroomCall {
+  Headroom* out;       // ksg_headroom: count structs
+  int32_t* out_nodes;  // ksg_headroom_nodes: N counts of pod `first`
+};
+// Queue pods [first, first + count) against the snapshot as the stream holds it:
+// the structs (or the one pod's node row) through the pinned block, one synchronisation
+int headroom_run(Engine& eng, uint32_t first, uint32_t count, void* user, std::string& err) {
+  Engine::Impl& I = *eng.impl();
+  const HeadroomCall& hc = *static_cast<const HeadroomCall*>(user);
+  const bool per_node = hc.out_nodes != nullptr;
+  const uint32_t N = I.N;
+  if (!I.F.n || I.F.pos_fit < 0) {  // (host.cpp checked the profile; the kernel reads a Fit profile)
+    err = "headroom: NodeResourcesFit is not in the profile";
+    return KSG_E_INVALID;
+  }
+  const size_t bytes = per_node ? (size_t)N * sizeof(int32_t) : (size_t)count * sizeof(Headroom);
+  if (!bytes) return KSG_OK;
+  auto run = [&]() -> bool {
+    if (!I.hr_dev.alloc(bytes, err)) return false;
+    if (I.hr_host_bytes < bytes) {
+      if (I.hr_host) HIPCHK(hipHostFree(I.hr_host));
+      I.hr_host = nullptr;
+      I.hr_host_bytes = 0;
+      HIPCHK(hipHostMalloc((void**)&I.hr_host, bytes, hipHostMallocDefault));
+      I.hr_host_bytes = bytes;
+    }
+    hipStream_t s = I.stream;
+    const uint32_t tiles = (N + kHrTile - 1) / kHrTile;
+    if (per_node) {
+      hipLaunchKernelGGL(k_headroom<true>, dim3(tiles), dim3(256), 0, s, I.cluster(), I.F, I.progs.p, I.prog_off_d.p, first,
+                         1u, (Headroom*)nullptr, reinterpret_cast<int32_t*>(I.hr_dev.p));
+    } else {
+      HIPCHK(hipMemsetAsync(I.hr_dev.p, 0, bytes, s));
+      for (uint32_t c0 = 0; tiles && c0 < count; c0 += kHrLaunchPods) {
+        const uint32_t cn = std::min(count - c0, kHrLaunchPods);
+        hipLaunchKernelGGL(k_headroom<false>, dim3(tiles, (cn + kHrPods - 1) / kHrPods), dim3(256), 0, s, I.cluster(), I.F,
+                           I.progs.p, I.prog_off_d.p, first + c0, cn, reinterpret_cast<Headroom*>(I.hr_dev.p) + c0,
+                           (int32_t*)nullptr);
+      }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(I.hr_host, I.hr_dev.p, bytes, hipMemcpyDeviceToHost, s));
+    return stream_sync(I, s, err);
+  };
+  if (!run()) return KSG_E_DEVICE;
+  if (per_node) {
+    std::memcpy(hc.out_nodes, I.hr_host, bytes);
+    return KSG_OK;
+  }
+  for (uint32_t i = 0; i < count; ++i) {  // the key back into its two fields
+    Headroom hr;
+    std::memcpy(&hr, I.hr_host + (size_t)i * sizeof(hr), sizeof(hr));
+    uint64_t key;
+    std::memcpy(&key, reinterpret_cast<const uint8_t*>(&hr) + kHrwKey * 4, sizeof(key));
+    hr.max_node = (int32_t)(key >> 32);
+    hr.best_node = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)key) : -1;
+    hc.out[i] = hr;
+  }
+  return KSG_OK;
+}
+}  // namespace
+
+// host.cpp: the context's lock, guard, shard, profile and range checks, the
+// programs of the range compiled if they are not yet, then fn on the engine
+int headroom_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const uint32_t* n_nodes, const char* what,
+                  int (*fn)(Engine& eng, uint32_t first, uint32_t count, void* user, std::string& err), void* user);
+
+}  // namespace ksg
+
+extern "C" int ksg_headroom(ksg_ctx* ctx, uint32_t first, uint32_t count, struct ksg_headroom* out) {
+  ksg::HeadroomCall hc{out, nullptr};
+  return ksg::headroom_call(ctx, first, count, out != nullptr, nullptr, "headroom", &ksg::headroom_run, &hc);
+}
+
+extern "C" int ksg_headroom_nodes(ksg_ctx* ctx, uint32_t q, int32_t* out, uint32_t n) {
+  ksg::HeadroomCall hc{nullptr, out};
+  return ksg::headroom_call(ctx, q, 1, out != nullptr, &n, "headroom_nodes", &ksg::headroom_run, &hc);
+}

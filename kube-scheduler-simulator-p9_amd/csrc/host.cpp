@@ -814,6 +814,7 @@ struct Cluster {
   int vkind[KSG_MAX_PROFILE] = {};  // VK_* of each profile position
   int n_dev = 0;
   bool has_volume_plugins = false;
+  string headroom_refusal;  // why ksg_headroom is not offered under this profile ("" : it is); load_profile
   Dict images;  // ImageLocality: every image name some node lists
   vector<std::pair<i64, int32_t>> image_state;  // per image: Size (first node listing it), NumNodes
   std::map<std::tuple<string, string, int32_t>, int32_t> port_id;  // host-port triples (ip, protocol, port)
@@ -965,6 +966,13 @@ struct Cluster {
     }
     ecfg.n_plugins = n_dev;
     ecfg.ba_n = (int)ba_res_names.size();
+    // headroom's closed form (include/ksg.h): replicas of a pod may interact through NodeResourcesFit alone
+    headroom_refusal = pos_of(P_FIT) < 0 ? "NodeResourcesFit is not in the profile" : "";
+    for (int i = 0; i < n_plugins && headroom_refusal.empty(); ++i) {
+      const int p = plugins[i];
+      if (p == P_PTS || p == P_IPA || p == P_PORTS || is_volume(p))
+        headroom_refusal = "replicas of a pod interact through the Filter of " + names[i] + ": no closed form";
+    }
     ecfg.ipa_hard_weight = ipa_hard;
     ecfg.ipa_ignore_existing_pref = ipa_ignore;
     return true;
@@ -5712,6 +5720,42 @@ int diag_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
   return KSG_OK;
 }
 }  // namespace ksg
+
+namespace ksg {
+// The same for headroom (ksg_headroom / ksg_headroom_nodes, csrc/headroom.hip): the
+// lock, the guard, the refusals (a sharded context, a profile outside the closed
+// form: KSG_E_INVALID), the argument / queue-range check and, with n_nodes, the
+// caller's node count against the local one (KSG_E_RANGE); the queue's programs
+// compiled if they are not yet (as ksg_whatif); then fn on the engine.
+int headroom_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const uint32_t* n_nodes, const char* what,
+                  int (*fn)(Engine& eng, uint32_t first, uint32_t count, void* user, std::string& err), void* user) {
+  KSG_LOCK(ctx);
+  KSG_GUARD(ctx);
+  auto& c = ctx->c;
+  if (c.shards > 1) return ctx->fail(std::string(what) + ": not offered on a sharded context", KSG_E_INVALID);
+  if (!c.headroom_refusal.empty()) return ctx->fail(std::string(what) + ": " + c.headroom_refusal, KSG_E_INVALID);
+  if (!args_ok || (uint64_t)first + count > c.queue.size() || (n_nodes && *n_nodes != c.hi - c.lo))
+    return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
+  if (!count) return KSG_OK;
+  if (!c.compile_queue()) return ctx->fail(c.err, KSG_E_INVALID);
+  if (!c.refresh_programs(first, count)) return ctx->fail(c.err, KSG_E_DEVICE);
+  const int rc = fn(*c.eng, first, count, user, c.err);
+  return rc == KSG_OK ? KSG_OK : ctx->fail(c.err, rc);
+}
+}  // namespace ksg
+
+// the name of resource column r (include/ksg.h)
+extern "C" int ksg_resource_name(const ksg_ctx* ctx, uint32_t r, char* buf, size_t cap, size_t* len) {
+  KSG_LOCK(ctx);
+  if (!ctx || !len) return KSG_E_INVALID;
+  *len = 0;
+  if (r >= ctx->c.res.names.size()) return KSG_E_RANGE;
+  const std::string& s = ctx->c.res.names[r];
+  *len = s.size();
+  if (!buf || cap < s.size()) return KSG_E_NOBUF;
+  std::memcpy(buf, s.data(), s.size());
+  return KSG_OK;
+}
 
 // diagnostic (not in ksg.h): out[2] = diagnosis calls (ksg_filter_histogram / ksg_fit_error)
 // answered from the device table so far, and by the host count of the kept filter row

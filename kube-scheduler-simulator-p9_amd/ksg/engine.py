@@ -4,6 +4,7 @@ from __future__ import annotations
 import ctypes
 import json
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -37,6 +38,18 @@ DIAG_MAX = 1024  # KSG_DIAG_MAX
 class _FilterBucket(ctypes.Structure):
     _fields_ = [("code", ctypes.c_uint32), ("pos", ctypes.c_int32), ("status", ctypes.c_int32),
                 ("count", ctypes.c_uint32)]
+
+
+HEADROOM_BOUNDS = 9  # KSG_HEADROOM_BOUNDS
+
+
+class _Headroom(ctypes.Structure):
+    _fields_ = [("replicas", ctypes.c_int64), ("nodes", ctypes.c_int32), ("open_nodes", ctypes.c_int32),
+                ("max_node", ctypes.c_int32), ("best_node", ctypes.c_int32),
+                ("bound", ctypes.c_uint32 * HEADROOM_BOUNDS)]
+
+
+Headroom = namedtuple("Headroom", "replicas nodes open_nodes max_node best_node bound")
 
 
 class _Opts(ctypes.Structure):
@@ -552,6 +565,44 @@ class Scheduler:
         self.L.ksg_debug_diag_routes.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._chk(self.L.ksg_debug_diag_routes(self.h, out), "ksg_debug_diag_routes")
         return out[0], out[1]
+
+    def headroom(self, first=0, count=None):
+        """ksg_headroom: for queue pods [first, first+count) how many more copies fit on the
+        snapshot as it stands: [Headroom(replicas, nodes, open_nodes, max_node, best_node, bound)],
+        bound a tuple over (pod room, resource columns...: resource_names()) of the open nodes
+        each constraint is the minimum on.  One launch for the whole range."""
+        # (bound on first use, like ranked_nodes: KSG_LIB may name an A/B build from before the call)
+        self.L.ksg_headroom.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_Headroom)]
+        count = self.queue_len - first if count is None else count
+        arr = (_Headroom * max(count, 1))()
+        self._chk(self.L.ksg_headroom(self.h, first, count, arr), "ksg_headroom")
+        return [Headroom(a.replicas, a.nodes, a.open_nodes, a.max_node, a.best_node, tuple(a.bound)) for a in arr[:count]]
+
+    def headroom_nodes(self, q):
+        """ksg_headroom_nodes: the per-node counts of queue pod q (local nodes)."""
+        self.L.ksg_headroom_nodes.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32),
+                                              ctypes.c_uint32]
+        n = self.n_nodes
+        arr = (ctypes.c_int32 * max(n, 1))()
+        self._chk(self.L.ksg_headroom_nodes(self.h, q, arr, n), "ksg_headroom_nodes")
+        return list(arr[:n])
+
+    def resource_names(self):
+        """ksg_resource_name for every resource column: the rows of node_requested() and bound[1:]."""
+        self.L.ksg_resource_name.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.c_size_t)]
+        out = []
+        while True:
+            n = ctypes.c_size_t()
+            buf = ctypes.create_string_buffer(256)
+            rc = self.L.ksg_resource_name(self.h, len(out), buf, 256, ctypes.byref(n))
+            if rc == -5:  # KSG_E_NOBUF: n holds the size
+                buf = ctypes.create_string_buffer(n.value)
+                rc = self.L.ksg_resource_name(self.h, len(out), buf, n.value, ctypes.byref(n))
+            if rc == -4:  # KSG_E_RANGE: past the last column
+                return out
+            self._chk(rc, "ksg_resource_name")
+            out.append(buf.raw[:n.value].decode())
 
     def node_nonzero(self):
         """NonZeroRequested (cpu milli, memory bytes) rows of every local node."""
