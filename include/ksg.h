@@ -51,7 +51,9 @@ extern "C" {
  * Added within 4 (no existing entry point or struct changed): ksg_ranked_nodes,
  * ksg_ranked_node, KSG_RANK_MAX; ksg_filter_histogram, ksg_fit_error,
  * ksg_filter_bucket, KSG_DIAG_MAX; ksg_headroom (the call and the struct),
- * ksg_headroom_nodes, ksg_resource_name, KSG_HEADROOM_BOUNDS. */
+ * ksg_headroom_nodes, ksg_resource_name, KSG_HEADROOM_BOUNDS; ksg_bound_count,
+ * ksg_bound_pod, ksg_bound_fit (the call and the struct), ksg_bound_fit_nodes,
+ * ksg_node_evictability, ksg_node_evict. */
 #define KSG_ABI_VERSION 4
 
 #define KSG_OK 0
@@ -406,6 +408,71 @@ struct ksg_headroom {
 int ksg_headroom(ksg_ctx* ctx, uint32_t first, uint32_t count, struct ksg_headroom* out);
 int ksg_headroom_nodes(ksg_ctx* ctx, uint32_t q, int32_t* out, uint32_t n);
 int ksg_resource_name(const ksg_ctx* ctx, uint32_t r, char* buf, size_t cap, size_t* len);
+
+/* Eviction fit (the descheduler's nodeFit and its taint / affinity / overcommit
+ * violation checks): which pods that are already running would their node no
+ * longer admit, and which of them has another node to go to -- every (bound pod,
+ * node) pair judged on the device (csrc/bound_fit.hip).
+ * Subjects.  b is the host's bound index: the document's pods with spec.nodeName,
+ * then the pods of addPod events, then the placed queue pods ksg_compact turned into
+ * bound pods.  ksg_bound_count counts them, ksg_bound_pod names one
+ * ("namespace/name", buffer convention of ksg_annotations; *node = its global node
+ * index, -1 when its node is not in the cluster).  An index is valid until the next
+ * ksg_load_cluster, ksg_apply_events or ksg_compact.  Queue pods placed since the
+ * last encode count as load on their nodes (the device rows hold them) but are
+ * not subjects: a caller who wants them calls ksg_compact(ksg_queue_len()) first.
+ * code(b, n), for bound pod b on node o, against the device snapshot as it stands
+ * when the call runs (every assume, Reserve and event applied so far; the call is
+ * ordered on the context stream after any pending delta): the Filter code
+ * ksg_filter_codes would report for node n after b was removed from the snapshot
+ * and run through ksg_cycle(commit = 0) with spec.nodeName cleared -- a bound pod's
+ * spec.nodeName is its placement, not a constraint, and its replacement comes from a
+ * controller without one, so NodeName's Filter is not applied.  In closed form:
+ *   n != o  the first failing Filter in profile order against n's current rows;
+ *   n == o  the same, NodeResourcesFit reading requested_r - request_r(b) for every
+ *           resource column and pod count - 1;
+ *   KSG_FILTER_NOT_EVALUATED when b's PreFilter rejects it or ends in an error, or n
+ *           is outside its PreFilterResult, as a cycle reports;
+ *   a pod whose requests are all zero is checked against the pod room alone, as
+ *           fitsRequest returns early;  KSG_FILTER_PASSED when every Filter passes.
+ * Codes are (position << 24) | detail, the detail of NodeResourcesFit its reason
+ * bits, as ksg_filter_codes.  Integer arithmetic throughout; exact.
+ * ksg_bound_fit fills out[i] for bound pods [first, first + count);
+ * ksg_bound_fit_nodes writes code(b, n) for every local node n: n must be the local
+ * node count (the convention of ksg_filter_codes).  ksg_node_evictability judges
+ * every bound pod and counts per local node (n: the local node count).  stuck is a
+ * necessary condition for a drain, not a sufficient one: each pod is judged alone,
+ * against the snapshot with only itself removed, so two pods counted as movable may
+ * compete for the same room.
+ * Profiles: those of ksg_headroom (NodeResourcesFit there; every plugin with a
+ * Filter one of NodeResourcesFit, TaintToleration, NodeAffinity, NodeUnschedulable,
+ * NodeName) -- under them removing b changes node o's rows only.  Any other:
+ * KSG_E_INVALID, the message naming the plugin.  A sharded context: KSG_E_INVALID.
+ * out NULL, the range outside [0, ksg_bound_count), n different from the local node
+ * count: KSG_E_RANGE.  count == 0: KSG_OK, nothing written.  The calls change no
+ * scheduling state and two calls return the same bytes.  The first call of a
+ * snapshot generation (after a load, an event batch, a compact) compiles every
+ * bound pod's program and uploads them, the store DefaultPreemption's victim
+ * search keeps; later calls find it resident.
+ * (C: `struct ksg_bound_fit` is named by its tag beside the call, as ksg_headroom.) */
+int ksg_bound_count(const ksg_ctx* ctx);
+int ksg_bound_pod(ksg_ctx* ctx, uint32_t b, char* buf, size_t cap, size_t* len, int32_t* node);
+struct ksg_bound_fit {          /* 16 bytes */
+  int32_t  node;         /* the node the pod is bound to (global index) */
+  uint32_t own_code;     /* code(b, own node): KSG_FILTER_PASSED when its node would admit it again */
+  int32_t  other_nodes;  /* nodes other than its own with code == KSG_FILTER_PASSED */
+  int32_t  first_other;  /* the lowest global index among them; -1 when other_nodes == 0 */
+};
+int ksg_bound_fit(ksg_ctx* ctx, uint32_t first, uint32_t count, struct ksg_bound_fit* out);
+int ksg_bound_fit_nodes(ksg_ctx* ctx, uint32_t b, uint32_t* codes, uint32_t n);
+struct ksg_node_evict {         /* 16 bytes, per local node */
+  int32_t pods;      /* bound pods on the node */
+  int32_t stuck;     /* of them, other_nodes == 0: nowhere else to go */
+  int32_t drifted;   /* of them, own_code != KSG_FILTER_PASSED: the node would not admit them today */
+  int32_t reserved;  /* 0 */
+};
+int ksg_node_evictability(ksg_ctx* ctx, struct ksg_node_evict* out, uint32_t n);
+
 /* PostFilter (wrappedplugin.go:550-577 -> store.go:442 AddPostFilterResult):
  * DefaultPreemption's dry run for an unschedulable pod q (PodEligibleToPreemptOthers,
  * nodesWherePreemptionMightHelp, SelectVictimsOnNode, pickOneNodeForPreemption of

@@ -1,0 +1,301 @@
+// Eviction fit (ksg_bound_fit / ksg_bound_fit_nodes / ksg_node_evictability,
+// include/ksg.h): for every bound pod, would its own node admit it again, and how
+// many other nodes would -- the headroom pass with the bound pods on the pod
+// axis.  Part of the engine's translation unit (engine.hip includes it after
+// headroom.hip).
+//
+//   k_bound_fit<false>  a (node tile x bound-pod tile) grid, the shape of
+//                 k_headroom.  A block of 256 threads owns kBfTile = 256 x kBfNpt
+//                 nodes: every thread loads its nodes' rows once, as free_r =
+//                 allocatable_r - requested_r for the R resource columns and left
+//                 = allowed - pod count, and keeps them in registers.  It then
+//                 walks the kBfPods bound pods of its tile over them.  A pod's
+//                 program lies in the victim store (its offset and the pod's own
+//                 local node index are wave-uniform reads, like its header and
+//                 requests).  The profile is walked in order: the static filters
+//                 are node_filter<kPmBoundFit> -- NodeName left out, a bound
+//                 pod's spec.nodeName is its placement -- and NodeResourcesFit is
+//                 fit_filter, the one body every kernel runs, over a register
+//                 source: allocatable() is free_r, requested() 0, allowed() left,
+//                 podcnt() 0.  On the one lane whose node is the pod's own the
+//                 source holds free_r + request_r and left + 1: the rows with the
+//                 pod taken off them.  The reject flags and the PreFilterResult
+//                 bitmask as k_headroom reads them.
+//   k_bound_fit<true>   the same body for one pod with a store of the code per node
+//                 (ksg_bound_fit_nodes).
+//   k_bound_fit_init    presets the structs: {node, KSG_FILTER_NOT_EVALUATED, 0, 0xFFFFFFFF}.
+//   k_node_evict  one thread per bound pod over the finished structs, three
+//                 atomicAdds into its node's row (ksg_node_evictability).
+//
+// Accumulation, all integer: per wave other_nodes is ballots and popcounts, and
+// the lowest passing node of the wave is read off the ballots (the lowest k with
+// a set bit, its lowest lane: a lane's nodes ascend with k); lane 0 adds / mins
+// them into the block's LDS pair of the pod; after the last pod the block issues
+// one global atomicAdd and one atomicMin per pod with a passing node.  own_code
+// is a plain store by the one lane of the grid whose node is the pod's own.  The
+// answer does not depend on the order in which waves and blocks arrive.
+//
+// Forward progress: no thread waits on another thread's progress (the barriers
+// are reached by every thread of the block: the pod and node loops hold no
+// return), and every loop is bounded by a tile constant, the profile length or
+// KSG_MAX_RES.
+#include "../../include/ksg.h"
+
+struct ksg_ctx;
+
+namespace ksg {
+
+using BoundFit = struct ::ksg_bound_fit;  // (the function of the same name hides the struct's)
+using NodeEvict = struct ::ksg_node_evict;
+constexpr uint32_t kBfNpt = 4;              // nodes per thread
+constexpr uint32_t kBfTile = 256 * kBfNpt;  // nodes per block
+constexpr uint32_t kBfPods = 32;            // bound pods per block (grid.y tiles)
+constexpr uint32_t kPmBoundFit = (1u << KP_TAINT) | (1u << KP_NA) | (1u << KP_UNSCHED);
+static_assert(sizeof(BoundFit) == 16 && offsetof(BoundFit, own_code) == 4 && offsetof(BoundFit, other_nodes) == 8 &&
+                  offsetof(BoundFit, first_other) == 12,
+              "the kernel accumulates into the struct's own layout");
+static_assert(sizeof(NodeEvict) == 16 && offsetof(NodeEvict, stuck) == 4 && offsetof(NodeEvict, drifted) == 8, "");
+
+// fit_filter's pod: the flags and the requests on the cluster's columns (0 beyond them)
+struct BfPod {
+  uint32_t flags;
+  int64_t req[KSG_MAX_RES];
+};
+// fit_filter's operand source over a node row held in registers, as what is left of it
+struct BfSrc {
+  const int64_t (&fr)[KSG_MAX_RES];
+  int32_t left;
+  __device__ __forceinline__ int64_t allocatable(int res) const { return fr[res]; }
+  __device__ __forceinline__ int64_t requested(int) const { return 0; }
+  __device__ __forceinline__ int32_t podcnt() const { return 0; }
+  __device__ __forceinline__ int32_t allowed() const { return left; }
+};
+
+__global__ __launch_bounds__(256) void k_bound_fit_init(const int32_t* __restrict__ own, uint32_t goff, uint32_t count,
+                                                        BoundFit* out) {
+  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= count) return;
+  const int32_t o = own[j];
+  BoundFit b;
+  b.node = o < 0 ? -1 : (int32_t)(goff + (uint32_t)o);
+  b.own_code = KSG_FILTER_NOT_EVALUATED;
+  b.other_nodes = 0;
+  b.first_other = (int32_t)0xFFFFFFFFu;
+  out[j] = b;
+}
+
+// off / own / out: entry 0 is the launch's first bound pod
+template <bool PER_NODE>
+__global__ __launch_bounds__(256) void k_bound_fit(DevCluster C, DevProfile F, const uint8_t* __restrict__ store,
+                                                   const uint64_t* __restrict__ off, const int32_t* __restrict__ own,
+                                                   uint32_t count, BoundFit* out, uint32_t* out_codes) {
+  __shared__ uint32_t acc[PER_NODE ? 1 : kBfPods][2];  // other_nodes, first_other (global index)
+  if (!PER_NODE) {
+    if (threadIdx.x < kBfPods) {
+      acc[threadIdx.x][0] = 0;
+      acc[threadIdx.x][1] = 0xFFFFFFFFu;
+    }
+    __syncthreads();
+  }
+  // the block's node rows, once
+  const uint32_t base = blockIdx.x * kBfTile + threadIdx.x;
+  int64_t fr[kBfNpt][KSG_MAX_RES];
+  int32_t left[kBfNpt];
+#pragma unroll
+  for (uint32_t k = 0; k < kBfNpt; ++k) {
+    const uint32_t n = base + k * 256;
+    const bool live = n < C.N;
+    left[k] = live ? C.allowed[n] - C.podcnt[n] : 0;
+#pragma unroll
+    for (uint32_t r = 0; r < KSG_MAX_RES; ++r)
+      fr[k][r] = (live && r < C.R) ? C.alloc[(size_t)r * C.N + n] - C.req[(size_t)r * C.N + n] : 0;
+  }
+#pragma unroll 1
+  for (uint32_t pi = 0; pi < kBfPods; ++pi) {
+    const uint32_t j = blockIdx.y * kBfPods + pi;
+    if (j >= count) break;  // (block-uniform)
+    const ProgView V = view(store + off[j]);
+    const ksg_prog* h = V.h;
+    const uint32_t flags = h->flags;
+    const uint32_t o = (uint32_t)own[j];  // (0xFFFFFFFF: its node is not in the snapshot; no lane holds it)
+    const bool rejected = (flags & (KPF_PREFILTER_REJECT | KPF_PREFILTER_ERROR)) != 0;
+    BfPod pod;
+    pod.flags = flags;
+#pragma unroll
+    for (uint32_t r = 0; r < KSG_MAX_RES; ++r) pod.req[r] = r < C.R ? h->req[r] : 0;
+    uint32_t code[kBfNpt];
+#pragma unroll
+    for (uint32_t k = 0; k < kBfNpt; ++k) {
+      const uint32_t n = base + k * 256;
+      code[k] = KSG_FILTER_NOT_EVALUATED;
+      if (n < C.N && !rejected &&
+          !((flags & KPF_RESTRICT) && !bit(V.u32 + h->restrict_off, h->restrict_words, (int32_t)n))) {
+        const bool home = n == o;  // the rows with the pod itself taken off them
+        int64_t f[KSG_MAX_RES];
+#pragma unroll
+        for (uint32_t r = 0; r < KSG_MAX_RES; ++r) f[r] = fr[k][r] + (home ? pod.req[r] : 0);
+        const BfSrc src{f, left[k] + (home ? 1 : 0)};
+        uint32_t c = KSG_FILTER_PASS;
+#pragma unroll 1
+        for (int pos = 0; pos < F.n && c == KSG_FILTER_PASS; ++pos) {
+          const int plugin = F.plugins[pos];
+          if (plugin == KP_FIT) {
+            const uint32_t detail = fit_filter(src, &pod, (uint32_t)KSG_MAX_RES);
+            if (detail) c = filter_code(pos, detail);
+          } else {
+            c = node_filter<kPmBoundFit>(plugin, pos, C, V, n);
+          }
+        }
+        code[k] = c;
+      }
+    }
+    if (PER_NODE) {
+#pragma unroll
+      for (uint32_t k = 0; k < kBfNpt; ++k) {
+        const uint32_t n = base + k * 256;
+        if (n < C.N) out_codes[n] = code[k];
+      }
+      continue;
+    }
+    // the wave's share of pod j, then lane 0 into the block's pair
+    uint32_t n_pass = 0, first = 0xFFFFFFFFu;
+#pragma unroll
+    for (uint32_t k = 0; k < kBfNpt; ++k) {
+      const uint32_t n = base + k * 256;
+      if (n == o) out[j].own_code = code[k];  // (n < C.N: o is a local node; one lane of the grid)
+      const unsigned long long b = __ballot(code[k] == KSG_FILTER_PASS && n != o);
+      if (!b) continue;  // (wave-uniform)
+      n_pass += (uint32_t)__popcll(b);
+      if (first == 0xFFFFFFFFu)
+        first = C.goff + blockIdx.x * kBfTile + (threadIdx.x & ~63u) + k * 256 + (uint32_t)__ffsll((long long)b) - 1;
+    }
+    if (n_pass && lane0()) {
+      atomicAdd(&acc[pi][0], n_pass);
+      atomicMin(&acc[pi][1], first);
+    }
+  }
+  if (PER_NODE) return;
+  __syncthreads();
+  // one global atomic per block and non-zero field
+  if (threadIdx.x < kBfPods) {
+    const uint32_t j = blockIdx.y * kBfPods + threadIdx.x;
+    if (j < count && acc[threadIdx.x][0]) {
+      atomicAdd(reinterpret_cast<uint32_t*>(&out[j].other_nodes), acc[threadIdx.x][0]);
+      atomicMin(reinterpret_cast<uint32_t*>(&out[j].first_other), acc[threadIdx.x][1]);
+    }
+  }
+}
+
+// ev: the local nodes' rows, zeroed
+__global__ __launch_bounds__(256) void k_node_evict(const BoundFit* __restrict__ fit, const int32_t* __restrict__ own,
+                                                    uint32_t count, uint32_t N, NodeEvict* ev) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= count) return;
+  const int32_t o = own[b];
+  if (o < 0 || (uint32_t)o >= N) return;
+  const BoundFit f = fit[b];
+  atomicAdd(&ev[o].pods, 1);
+  if (f.other_nodes == 0) atomicAdd(&ev[o].stuck, 1);
+  if (f.own_code != KSG_FILTER_PASS) atomicAdd(&ev[o].drifted, 1);
+}
+
+namespace {
+// one launch covers at most this many bound pods (grid.y <= 65535)
+constexpr uint32_t kBfLaunchPods = 65535u * kBfPods;
+
+// Bound pods [first, first + count) against the snapshot as the stream holds it:
+// the structs, the one pod's code row or (the range being every bound pod) the
+// node rows, through the pinned block, one synchronisation.  Filter codes leave
+// with device positions: host.cpp turns them into profile positions.
+int bound_fit_run(Engine& eng, uint32_t first, uint32_t count, const int32_t* own, const BoundFitOut& bo,
+                  std::string& err) {
+  Engine::Impl& I = *eng.impl();
+  const uint32_t N = I.N;
+  if (!I.F.n || I.F.pos_fit < 0) {  // (host.cpp checked the profile; the kernel reads a Fit profile)
+    err = "bound_fit: NodeResourcesFit is not in the profile";
+    return KSG_E_INVALID;
+  }
+  if ((size_t)first + count > I.vstore_off.size()) {  // (host.cpp ensured the store for this very bound list)
+    err = "bound_fit: bound pod outside the victim store";
+    return KSG_E_STATE;
+  }
+  const bool per_node = bo.codes != nullptr, evict = bo.evict != nullptr;
+  const size_t fit_bytes = per_node ? 0 : (size_t)count * sizeof(BoundFit);
+  const size_t row_bytes = per_node ? (size_t)N * sizeof(uint32_t) : evict ? (size_t)N * sizeof(NodeEvict) : 0;
+  const size_t back_bytes = evict || per_node ? row_bytes : fit_bytes;  // what crosses the host link
+  if (!back_bytes) return KSG_OK;
+  // the launch inputs: every pod's offset into the store, then its own local node
+  const size_t in_bytes = (size_t)count * (sizeof(uint64_t) + sizeof(int32_t));
+  std::vector<uint8_t> in(in_bytes);
+  {
+    uint64_t* o64 = reinterpret_cast<uint64_t*>(in.data());
+    for (uint32_t i = 0; i < count; ++i) o64[i] = I.vstore_off[(size_t)first + i];
+    if (count) std::memcpy(in.data() + (size_t)count * sizeof(uint64_t), own + first, (size_t)count * sizeof(int32_t));
+  }
+  auto run = [&]() -> bool {
+    if (!I.bf_in.alloc(in_bytes, err) || !I.hr_dev.alloc(fit_bytes + row_bytes, err)) return false;
+    if (I.hr_host_bytes < back_bytes) {
+      if (I.hr_host) HIPCHK(hipHostFree(I.hr_host));
+      I.hr_host = nullptr;
+      I.hr_host_bytes = 0;
+      HIPCHK(hipHostMalloc((void**)&I.hr_host, back_bytes, hipHostMallocDefault));
+      I.hr_host_bytes = back_bytes;
+    }
+    hipStream_t s = I.stream;
+    const uint64_t* d_off = reinterpret_cast<const uint64_t*>(I.bf_in.p);
+    const int32_t* d_own = reinterpret_cast<const int32_t*>(I.bf_in.p + (size_t)count * sizeof(uint64_t));
+    BoundFit* d_fit = reinterpret_cast<BoundFit*>(I.hr_dev.p);
+    uint8_t* d_row = I.hr_dev.p + fit_bytes;
+    const uint32_t tiles = (N + kBfTile - 1) / kBfTile;
+    if (in_bytes) HIPCHK(hipMemcpyAsync(I.bf_in.p, in.data(), in_bytes, hipMemcpyHostToDevice, s));
+    if (per_node) {
+      hipLaunchKernelGGL(k_bound_fit<true>, dim3(tiles), dim3(256), 0, s, I.cluster(), I.F, I.vstore.p, d_off, d_own, 1u,
+                         (BoundFit*)nullptr, reinterpret_cast<uint32_t*>(d_row));
+    } else {
+      if (count)
+        hipLaunchKernelGGL(k_bound_fit_init, dim3((count + 255) / 256), dim3(256), 0, s, d_own, I.cluster().goff, count,
+                           d_fit);
+      for (uint32_t c0 = 0; tiles && c0 < count; c0 += kBfLaunchPods) {
+        const uint32_t cn = std::min(count - c0, kBfLaunchPods);
+        hipLaunchKernelGGL(k_bound_fit<false>, dim3(tiles, (cn + kBfPods - 1) / kBfPods), dim3(256), 0, s, I.cluster(), I.F,
+                           I.vstore.p, d_off + c0, d_own + c0, cn, d_fit + c0, (uint32_t*)nullptr);
+      }
+      if (evict) {
+        HIPCHK(hipMemsetAsync(d_row, 0, row_bytes, s));
+        if (count)
+          hipLaunchKernelGGL(k_node_evict, dim3((count + 255) / 256), dim3(256), 0, s, d_fit, d_own, count, N,
+                             reinterpret_cast<NodeEvict*>(d_row));
+      }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(I.hr_host, evict || per_node ? d_row : reinterpret_cast<uint8_t*>(d_fit), back_bytes,
+                          hipMemcpyDeviceToHost, s));
+    return stream_sync(I, s, err);
+  };
+  if (!run()) return KSG_E_DEVICE;
+  std::memcpy(per_node ? (void*)bo.codes : evict ? (void*)bo.evict : (void*)bo.fit, I.hr_host, back_bytes);
+  return KSG_OK;
+}
+}  // namespace
+
+// host.cpp: the context's lock, guard, shard, profile and range checks, the
+// victim store ensured, then fn on the engine and the codes' positions translated
+int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, bool args_ok, const uint32_t* n_nodes,
+                   const char* what, BoundFitFn fn, const BoundFitOut& bo);
+
+}  // namespace ksg
+
+extern "C" int ksg_bound_fit(ksg_ctx* ctx, uint32_t first, uint32_t count, struct ksg_bound_fit* out) {
+  return ksg::bound_fit_call(ctx, first, count, false, out != nullptr, nullptr, "bound_fit", &ksg::bound_fit_run,
+                             ksg::BoundFitOut{out, nullptr, nullptr});
+}
+
+extern "C" int ksg_bound_fit_nodes(ksg_ctx* ctx, uint32_t b, uint32_t* codes, uint32_t n) {
+  return ksg::bound_fit_call(ctx, b, 1, false, codes != nullptr, &n, "bound_fit_nodes", &ksg::bound_fit_run,
+                             ksg::BoundFitOut{nullptr, codes, nullptr});
+}
+
+extern "C" int ksg_node_evictability(ksg_ctx* ctx, struct ksg_node_evict* out, uint32_t n) {
+  return ksg::bound_fit_call(ctx, 0, 0, true, out != nullptr, &n, "node_evictability", &ksg::bound_fit_run,
+                             ksg::BoundFitOut{nullptr, nullptr, out});
+}

@@ -11,6 +11,8 @@
 #include "ksg_types.h"
 
 struct ksg_filter_bucket;  // include/ksg.h
+struct ksg_bound_fit;
+struct ksg_node_evict;
 
 namespace ksg {
 
@@ -351,5 +353,18 @@ struct DiagRequest {
   size_t bcap;
   size_t* len;
 };
+
+// What an eviction-fit entry point (bound_fit.hip) asks of host.cpp's
+// bound_fit_call: exactly one of the structs of ksg_bound_fit, the code row of
+// ksg_bound_fit_nodes, the node rows of ksg_node_evictability.  The engine
+// function gets the range and own[b], every bound pod's local node index (-1:
+// its node is not in the snapshot).
+struct BoundFitOut {
+  struct ::ksg_bound_fit* fit;
+  uint32_t* codes;
+  struct ::ksg_node_evict* evict;
+};
+using BoundFitFn = int (*)(Engine& eng, uint32_t first, uint32_t count, const int32_t* own, const BoundFitOut& out,
+                           std::string& err);
 
 }  // namespace ksg

@@ -5560,7 +5560,10 @@ struct Engine::Impl {
   DBuf<uint8_t> hr_dev;
   uint8_t* hr_host = nullptr;
   size_t hr_host_bytes = 0;
-  DBuf<int32_t> knorm;    // normalized scores of one kept pod
+  // eviction fit (bound_fit.hip): a launch's inputs, the bound pods' store offsets and own nodes
+  // (its results use headroom's device and pinned blocks: the context lock serialises the calls)
+  DBuf<uint8_t> bf_in;
+  DBuf<int32_t> knorm;   // normalized scores of one kept pod
   DBuf<uint8_t> vblk;     // device cycle view block (Engine::view)
   bool vblk_fresh = true;
   uint32_t vgen = 0;      // view generation (slot-table entries of older views count as empty)
@@ -8567,3 +8570,4 @@ extern "C" int ksg_debug_arith(int op, const int64_t* in, uint32_t cols, int64_t
 #include "ranked.hip"
 #include "diagnosis.hip"
 #include "headroom.hip"
+#include "bound_fit.hip"

@@ -1709,6 +1709,20 @@ struct Cluster {
     bcsr_gen = bprog_gen;
     return bcsr_off;
   }
+  // every bound pod's local node index (-1: its node is not in this snapshot), for the
+  // eviction-fit kernels (bound_fit.hip); rebuilt when bprog_gen moves
+  vector<int32_t> bown;
+  uint64_t bown_gen = ~0ull;
+  const vector<int32_t>& bound_own_nodes() {
+    if (bown_gen == bprog_gen && bown.size() == bound.size()) return bown;
+    bown.assign(bound.size(), -1);
+    for (size_t b = 0; b < bound.size(); ++b) {
+      const int32_t g = node_names.get(bound[b].node);
+      if (g >= (int32_t)lo && g < (int32_t)hi) bown[b] = g - (int32_t)lo;
+    }
+    bown_gen = bprog_gen;
+    return bown;
+  }
   // The device-resident victim store (Engine::victim_store): every bound pod's
   // program, current while bprog_gen and the class registry hold.
   // bound victims that make a search upload the store (KSG_VICTIM_STORE_MIN: tests force it)
@@ -5743,6 +5757,61 @@ int headroom_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, co
   return rc == KSG_OK ? KSG_OK : ctx->fail(c.err, rc);
 }
 }  // namespace ksg
+
+namespace ksg {
+// The same for the eviction fit (ksg_bound_fit / ksg_bound_fit_nodes /
+// ksg_node_evictability, csrc/bound_fit.hip): the lock, the guard, headroom's
+// refusals (under its profiles removing a bound pod changes its own node's rows
+// only), the argument / bound-range check and, with n_nodes, the caller's node
+// count against the local one (KSG_E_RANGE); whole: the range is every bound pod.
+// The victim store is ensured whether or not DefaultPreemption is in the
+// profile: per snapshot generation the first call compiles every bound pod's
+// program (the queue's classes first: the store is built against them).  Then
+// fn on the engine, and the codes from device to profile positions.
+int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, bool args_ok, const uint32_t* n_nodes,
+                   const char* what, BoundFitFn fn, const BoundFitOut& bo) {
+  KSG_LOCK(ctx);
+  KSG_GUARD(ctx);
+  auto& c = ctx->c;
+  if (c.shards > 1) return ctx->fail(std::string(what) + ": not offered on a sharded context", KSG_E_INVALID);
+  if (!c.headroom_refusal.empty()) return ctx->fail(std::string(what) + ": " + c.headroom_refusal, KSG_E_INVALID);
+  if (whole) {
+    first = 0;
+    count = (uint32_t)c.bound.size();
+  }
+  if (!args_ok || (uint64_t)first + count > c.bound.size() || (n_nodes && *n_nodes != c.hi - c.lo))
+    return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
+  if (!count && !whole) return KSG_OK;
+  if (!c.compile_queue()) return ctx->fail(c.err, KSG_E_INVALID);
+  if (!c.ensure_victim_store()) return ctx->fail(c.err, KSG_E_DEVICE);
+  const std::vector<int32_t>& own = c.bound_own_nodes();
+  const int rc = fn(*c.eng, first, count, own.data(), bo, c.err);
+  if (rc != KSG_OK) return ctx->fail(c.err, rc);
+  auto profile_code = [&](uint32_t code) {
+    return code >= KSG_FILTER_NOT_EVALUATED ? code : ((uint32_t)c.code_pos(code) << 24) | c.code_detail(code);
+  };
+  if (bo.fit)
+    for (uint32_t i = 0; i < count; ++i) bo.fit[i].own_code = profile_code(bo.fit[i].own_code);
+  if (bo.codes)
+    for (uint32_t i = 0; i < c.hi - c.lo; ++i) bo.codes[i] = profile_code(bo.codes[i]);
+  return KSG_OK;
+}
+}  // namespace ksg
+
+// the bound pods, the subjects of the eviction fit (include/ksg.h); host state only
+extern "C" int ksg_bound_count(const ksg_ctx* ctx) {
+  KSG_LOCK(ctx);
+  return ctx ? (int)ctx->c.bound.size() : 0;
+}
+extern "C" int ksg_bound_pod(ksg_ctx* ctx, uint32_t b, char* buf, size_t cap, size_t* len, int32_t* node) {
+  KSG_LOCK(ctx);
+  if (!ctx || !len) return KSG_E_INVALID;
+  *len = 0;
+  if (b >= ctx->c.bound.size()) return KSG_E_RANGE;
+  const auto& p = ctx->c.bound[b];
+  if (node) *node = std::max<int32_t>(ctx->c.node_names.get(p.node), -1);
+  return put_str(nullptr, p.ns + "/" + p.name, buf, cap, len);
+}
 
 // the name of resource column r (include/ksg.h)
 extern "C" int ksg_resource_name(const ksg_ctx* ctx, uint32_t r, char* buf, size_t cap, size_t* len) {

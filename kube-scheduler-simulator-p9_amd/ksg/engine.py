@@ -52,6 +52,20 @@ class _Headroom(ctypes.Structure):
 Headroom = namedtuple("Headroom", "replicas nodes open_nodes max_node best_node bound")
 
 
+class _BoundFit(ctypes.Structure):
+    _fields_ = [("node", ctypes.c_int32), ("own_code", ctypes.c_uint32), ("other_nodes", ctypes.c_int32),
+                ("first_other", ctypes.c_int32)]
+
+
+class _NodeEvict(ctypes.Structure):
+    _fields_ = [("pods", ctypes.c_int32), ("stuck", ctypes.c_int32), ("drifted", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+BoundFit = namedtuple("BoundFit", "node own_code other_nodes first_other")
+NodeEvict = namedtuple("NodeEvict", "pods stuck drifted")
+
+
 class _Opts(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("stream", ctypes.c_void_p), ("shard_rank", ctypes.c_uint32),
                 ("shard_count", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
@@ -603,6 +617,59 @@ class Scheduler:
                 return out
             self._chk(rc, "ksg_resource_name")
             out.append(buf.raw[:n.value].decode())
+
+    # ---- eviction fit (ksg.h): the bound pods against the snapshot with themselves removed
+    @property
+    def bound_count(self):
+        self.L.ksg_bound_count.argtypes = [ctypes.c_void_p]
+        return self.L.ksg_bound_count(self.h)
+
+    def bound_pods(self):
+        """ksg_bound_pod for every bound pod: [("namespace/name", global node index)], entry b the
+        subject b of bound_fit(); valid until the next load_cluster, apply_events or compact."""
+        self.L.ksg_bound_pod.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t,
+                                         ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32)]
+        out = []
+        for b in range(self.bound_count):
+            n, node = ctypes.c_size_t(), ctypes.c_int32()
+            buf = ctypes.create_string_buffer(1024)
+            rc = self.L.ksg_bound_pod(self.h, b, buf, 1024, ctypes.byref(n), ctypes.byref(node))
+            if rc == -5:  # KSG_E_NOBUF: n holds the size
+                buf = ctypes.create_string_buffer(n.value)
+                rc = self.L.ksg_bound_pod(self.h, b, buf, n.value, ctypes.byref(n), ctypes.byref(node))
+            self._chk(rc, "ksg_bound_pod")
+            out.append((buf.raw[:n.value].decode(), node.value))
+        return out
+
+    def bound_fit(self, first=0, count=None):
+        """ksg_bound_fit: for bound pods [first, first+count), with the pod itself taken off the
+        snapshot: [BoundFit(node, own_code, other_nodes, first_other)] -- the filter code of its own
+        node (FILTER_PASSED: it would be admitted again), how many other nodes pass every Filter,
+        and the lowest of them (-1 none).  One pass on the device for the whole range."""
+        self.L.ksg_bound_fit.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_BoundFit)]
+        count = self.bound_count - first if count is None else count
+        arr = (_BoundFit * max(count, 1))()
+        self._chk(self.L.ksg_bound_fit(self.h, first, count, arr), "ksg_bound_fit")
+        return [BoundFit(a.node, a.own_code, a.other_nodes, a.first_other) for a in arr[:count]]
+
+    def bound_fit_nodes(self, b):
+        """ksg_bound_fit_nodes: bound pod b's filter code on every local node (as filter_codes)."""
+        self.L.ksg_bound_fit_nodes.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                               ctypes.c_uint32]
+        n = self.n_nodes
+        arr = (ctypes.c_uint32 * max(n, 1))()
+        self._chk(self.L.ksg_bound_fit_nodes(self.h, b, arr, n), "ksg_bound_fit_nodes")
+        return list(arr[:n])
+
+    def node_evictability(self):
+        """ksg_node_evictability: per local node NodeEvict(pods, stuck, drifted) -- its bound pods,
+        those with no other node to go to, those it would not admit today.  Each pod is judged
+        alone: stuck == 0 is necessary for a drain, not sufficient."""
+        self.L.ksg_node_evictability.argtypes = [ctypes.c_void_p, ctypes.POINTER(_NodeEvict), ctypes.c_uint32]
+        n = self.n_nodes
+        arr = (_NodeEvict * max(n, 1))()
+        self._chk(self.L.ksg_node_evictability(self.h, arr, n), "ksg_node_evictability")
+        return [NodeEvict(a.pods, a.stuck, a.drifted) for a in arr[:n]]
 
     def node_nonzero(self):
         """NonZeroRequested (cpu milli, memory bytes) rows of every local node."""
