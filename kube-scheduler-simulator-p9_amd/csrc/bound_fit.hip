@@ -4,23 +4,17 @@
 // axis.  Part of the engine's translation unit (engine.hip includes it after
 // headroom.hip).
 //
-//   k_bound_fit<false>  a (node tile x bound-pod tile) grid, the shape of
-//                 k_headroom.  A block of 256 threads owns kBfTile = 256 x kBfNpt
-//                 nodes: every thread loads its nodes' rows once, as free_r =
-//                 allocatable_r - requested_r for the R resource columns and left
-//                 = allowed - pod count, and keeps them in registers.  It then
-//                 walks the kBfPods bound pods of its tile over them.  A pod's
+//   k_bound_fit<false>  the (node tile x pod tile) grid of snapshot_query.hip
+//                 over the bound pods: sq_rows' rows, the gate sq_live.  A pod's
 //                 program lies in the victim store (its offset and the pod's own
 //                 local node index are wave-uniform reads, like its header and
-//                 requests).  The profile is walked in order: the static filters
-//                 are node_filter<kPmBoundFit> -- NodeName left out, a bound
-//                 pod's spec.nodeName is its placement -- and NodeResourcesFit is
-//                 fit_filter, the one body every kernel runs, over a register
-//                 source: allocatable() is free_r, requested() 0, allowed() left,
-//                 podcnt() 0.  On the one lane whose node is the pod's own the
-//                 source holds free_r + request_r and left + 1: the rows with the
-//                 pod taken off them.  The reject flags and the PreFilterResult
-//                 bitmask as k_headroom reads them.
+//                 requests).  The profile is walked in order, sq_walk<kPmBoundFit>
+//                 -- NodeName left out, a bound pod's spec.nodeName is its
+//                 placement -- and NodeResourcesFit is fit_filter, the one body
+//                 every kernel runs, over a register source: allocatable() is
+//                 free_r, requested() 0, allowed() left, podcnt() 0.  On the one
+//                 lane whose node is the pod's own the source holds free_r +
+//                 request_r and left + 1: the rows with the pod taken off them.
 //   k_bound_fit<true>   the same body for one pod with a store of the code per node
 //                 (ksg_bound_fit_nodes).
 //   k_bound_fit_init    presets the structs: {node, KSG_FILTER_NOT_EVALUATED, 0, 0xFFFFFFFF}.
@@ -35,21 +29,13 @@
 // is a plain store by the one lane of the grid whose node is the pod's own.  The
 // answer does not depend on the order in which waves and blocks arrive.
 //
-// Forward progress: no thread waits on another thread's progress (the barriers
-// are reached by every thread of the block: the pod and node loops hold no
-// return), and every loop is bounded by a tile constant, the profile length or
-// KSG_MAX_RES.
+// Forward progress: snapshot_query.hip's argument; the loops below hold no return.
 #include "../../include/ksg.h"
-
-struct ksg_ctx;
 
 namespace ksg {
 
 using BoundFit = struct ::ksg_bound_fit;  // (the function of the same name hides the struct's)
 using NodeEvict = struct ::ksg_node_evict;
-constexpr uint32_t kBfNpt = 4;              // nodes per thread
-constexpr uint32_t kBfTile = 256 * kBfNpt;  // nodes per block
-constexpr uint32_t kBfPods = 32;            // bound pods per block (grid.y tiles)
 constexpr uint32_t kPmBoundFit = (1u << KP_TAINT) | (1u << KP_NA) | (1u << KP_UNSCHED);
 static_assert(sizeof(BoundFit) == 16 && offsetof(BoundFit, own_code) == 4 && offsetof(BoundFit, other_nodes) == 8 &&
                   offsetof(BoundFit, first_other) == 12,
@@ -89,69 +75,48 @@ template <bool PER_NODE>
 __global__ __launch_bounds__(256) void k_bound_fit(DevCluster C, DevProfile F, const uint8_t* __restrict__ store,
                                                    const uint64_t* __restrict__ off, const int32_t* __restrict__ own,
                                                    uint32_t count, BoundFit* out, uint32_t* out_codes) {
-  __shared__ uint32_t acc[PER_NODE ? 1 : kBfPods][2];  // other_nodes, first_other (global index)
+  __shared__ uint32_t acc[PER_NODE ? 1 : kSqPods][2];  // other_nodes, first_other (global index)
   if (!PER_NODE) {
-    if (threadIdx.x < kBfPods) {
+    if (threadIdx.x < kSqPods) {
       acc[threadIdx.x][0] = 0;
       acc[threadIdx.x][1] = 0xFFFFFFFFu;
     }
     __syncthreads();
   }
   // the block's node rows, once
-  const uint32_t base = blockIdx.x * kBfTile + threadIdx.x;
-  int64_t fr[kBfNpt][KSG_MAX_RES];
-  int32_t left[kBfNpt];
-#pragma unroll
-  for (uint32_t k = 0; k < kBfNpt; ++k) {
-    const uint32_t n = base + k * 256;
-    const bool live = n < C.N;
-    left[k] = live ? C.allowed[n] - C.podcnt[n] : 0;
-#pragma unroll
-    for (uint32_t r = 0; r < KSG_MAX_RES; ++r)
-      fr[k][r] = (live && r < C.R) ? C.alloc[(size_t)r * C.N + n] - C.req[(size_t)r * C.N + n] : 0;
-  }
+  const uint32_t base = blockIdx.x * kSqTile + threadIdx.x;
+  int64_t fr[kSqNpt][KSG_MAX_RES];
+  int32_t left[kSqNpt];
+  sq_rows(C, base, fr, left);
 #pragma unroll 1
-  for (uint32_t pi = 0; pi < kBfPods; ++pi) {
-    const uint32_t j = blockIdx.y * kBfPods + pi;
+  for (uint32_t pi = 0; pi < kSqPods; ++pi) {
+    const uint32_t j = blockIdx.y * kSqPods + pi;
     if (j >= count) break;  // (block-uniform)
     const ProgView V = view(store + off[j]);
     const ksg_prog* h = V.h;
     const uint32_t flags = h->flags;
     const uint32_t o = (uint32_t)own[j];  // (0xFFFFFFFF: its node is not in the snapshot; no lane holds it)
-    const bool rejected = (flags & (KPF_PREFILTER_REJECT | KPF_PREFILTER_ERROR)) != 0;
     BfPod pod;
     pod.flags = flags;
 #pragma unroll
     for (uint32_t r = 0; r < KSG_MAX_RES; ++r) pod.req[r] = r < C.R ? h->req[r] : 0;
-    uint32_t code[kBfNpt];
+    uint32_t code[kSqNpt];
 #pragma unroll
-    for (uint32_t k = 0; k < kBfNpt; ++k) {
+    for (uint32_t k = 0; k < kSqNpt; ++k) {
       const uint32_t n = base + k * 256;
       code[k] = KSG_FILTER_NOT_EVALUATED;
-      if (n < C.N && !rejected &&
-          !((flags & KPF_RESTRICT) && !bit(V.u32 + h->restrict_off, h->restrict_words, (int32_t)n))) {
+      if (sq_live(C, V, n)) {
         const bool home = n == o;  // the rows with the pod itself taken off them
         int64_t f[KSG_MAX_RES];
 #pragma unroll
         for (uint32_t r = 0; r < KSG_MAX_RES; ++r) f[r] = fr[k][r] + (home ? pod.req[r] : 0);
         const BfSrc src{f, left[k] + (home ? 1 : 0)};
-        uint32_t c = KSG_FILTER_PASS;
-#pragma unroll 1
-        for (int pos = 0; pos < F.n && c == KSG_FILTER_PASS; ++pos) {
-          const int plugin = F.plugins[pos];
-          if (plugin == KP_FIT) {
-            const uint32_t detail = fit_filter(src, &pod, (uint32_t)KSG_MAX_RES);
-            if (detail) c = filter_code(pos, detail);
-          } else {
-            c = node_filter<kPmBoundFit>(plugin, pos, C, V, n);
-          }
-        }
-        code[k] = c;
+        code[k] = sq_walk<kPmBoundFit>(C, F, V, n, [&] { return fit_filter(src, &pod, (uint32_t)KSG_MAX_RES); });
       }
     }
     if (PER_NODE) {
 #pragma unroll
-      for (uint32_t k = 0; k < kBfNpt; ++k) {
+      for (uint32_t k = 0; k < kSqNpt; ++k) {
         const uint32_t n = base + k * 256;
         if (n < C.N) out_codes[n] = code[k];
       }
@@ -160,14 +125,14 @@ __global__ __launch_bounds__(256) void k_bound_fit(DevCluster C, DevProfile F, c
     // the wave's share of pod j, then lane 0 into the block's pair
     uint32_t n_pass = 0, first = 0xFFFFFFFFu;
 #pragma unroll
-    for (uint32_t k = 0; k < kBfNpt; ++k) {
+    for (uint32_t k = 0; k < kSqNpt; ++k) {
       const uint32_t n = base + k * 256;
       if (n == o) out[j].own_code = code[k];  // (n < C.N: o is a local node; one lane of the grid)
       const unsigned long long b = __ballot(code[k] == KSG_FILTER_PASS && n != o);
       if (!b) continue;  // (wave-uniform)
       n_pass += (uint32_t)__popcll(b);
       if (first == 0xFFFFFFFFu)
-        first = C.goff + blockIdx.x * kBfTile + (threadIdx.x & ~63u) + k * 256 + (uint32_t)__ffsll((long long)b) - 1;
+        first = C.goff + blockIdx.x * kSqTile + (threadIdx.x & ~63u) + k * 256 + (uint32_t)__ffsll((long long)b) - 1;
     }
     if (n_pass && lane0()) {
       atomicAdd(&acc[pi][0], n_pass);
@@ -177,8 +142,8 @@ __global__ __launch_bounds__(256) void k_bound_fit(DevCluster C, DevProfile F, c
   if (PER_NODE) return;
   __syncthreads();
   // one global atomic per block and non-zero field
-  if (threadIdx.x < kBfPods) {
-    const uint32_t j = blockIdx.y * kBfPods + threadIdx.x;
+  if (threadIdx.x < kSqPods) {
+    const uint32_t j = blockIdx.y * kSqPods + threadIdx.x;
     if (j < count && acc[threadIdx.x][0]) {
       atomicAdd(reinterpret_cast<uint32_t*>(&out[j].other_nodes), acc[threadIdx.x][0]);
       atomicMin(reinterpret_cast<uint32_t*>(&out[j].first_other), acc[threadIdx.x][1]);
@@ -200,9 +165,6 @@ __global__ __launch_bounds__(256) void k_node_evict(const BoundFit* __restrict__
 }
 
 namespace {
-// one launch covers at most this many bound pods (grid.y <= 65535)
-constexpr uint32_t kBfLaunchPods = 65535u * kBfPods;
-
 // Bound pods [first, first + count) against the snapshot as the stream holds it:
 // the structs, the one pod's code row or (the range being every bound pod) the
 // node rows, through the pinned block, one synchronisation.  Filter codes leave
@@ -232,56 +194,38 @@ int bound_fit_run(Engine& eng, uint32_t first, uint32_t count, const int32_t* ow
     for (uint32_t i = 0; i < count; ++i) o64[i] = I.vstore_off[(size_t)first + i];
     if (count) std::memcpy(in.data() + (size_t)count * sizeof(uint64_t), own + first, (size_t)count * sizeof(int32_t));
   }
-  auto run = [&]() -> bool {
-    if (!I.bf_in.alloc(in_bytes, err) || !I.hr_dev.alloc(fit_bytes + row_bytes, err)) return false;
-    if (I.hr_host_bytes < back_bytes) {
-      if (I.hr_host) HIPCHK(hipHostFree(I.hr_host));
-      I.hr_host = nullptr;
-      I.hr_host_bytes = 0;
-      HIPCHK(hipHostMalloc((void**)&I.hr_host, back_bytes, hipHostMallocDefault));
-      I.hr_host_bytes = back_bytes;
-    }
-    hipStream_t s = I.stream;
-    const uint64_t* d_off = reinterpret_cast<const uint64_t*>(I.bf_in.p);
-    const int32_t* d_own = reinterpret_cast<const int32_t*>(I.bf_in.p + (size_t)count * sizeof(uint64_t));
-    BoundFit* d_fit = reinterpret_cast<BoundFit*>(I.hr_dev.p);
-    uint8_t* d_row = I.hr_dev.p + fit_bytes;
-    const uint32_t tiles = (N + kBfTile - 1) / kBfTile;
+  if (!I.bf_in.alloc(in_bytes, err) || !I.hr_dev.alloc(fit_bytes + row_bytes, err)) return KSG_E_DEVICE;
+  const uint64_t* d_off = reinterpret_cast<const uint64_t*>(I.bf_in.p);
+  const int32_t* d_own = reinterpret_cast<const int32_t*>(I.bf_in.p + (size_t)count * sizeof(uint64_t));
+  BoundFit* d_fit = reinterpret_cast<BoundFit*>(I.hr_dev.p);
+  uint8_t* d_row = I.hr_dev.p + fit_bytes;
+  auto enqueue = [&](hipStream_t s) -> bool {
     if (in_bytes) HIPCHK(hipMemcpyAsync(I.bf_in.p, in.data(), in_bytes, hipMemcpyHostToDevice, s));
     if (per_node) {
-      hipLaunchKernelGGL(k_bound_fit<true>, dim3(tiles), dim3(256), 0, s, I.cluster(), I.F, I.vstore.p, d_off, d_own, 1u,
-                         (BoundFit*)nullptr, reinterpret_cast<uint32_t*>(d_row));
-    } else {
-      if (count)
-        hipLaunchKernelGGL(k_bound_fit_init, dim3((count + 255) / 256), dim3(256), 0, s, d_own, I.cluster().goff, count,
-                           d_fit);
-      for (uint32_t c0 = 0; tiles && c0 < count; c0 += kBfLaunchPods) {
-        const uint32_t cn = std::min(count - c0, kBfLaunchPods);
-        hipLaunchKernelGGL(k_bound_fit<false>, dim3(tiles, (cn + kBfPods - 1) / kBfPods), dim3(256), 0, s, I.cluster(), I.F,
-                           I.vstore.p, d_off + c0, d_own + c0, cn, d_fit + c0, (uint32_t*)nullptr);
-      }
-      if (evict) {
-        HIPCHK(hipMemsetAsync(d_row, 0, row_bytes, s));
-        if (count)
-          hipLaunchKernelGGL(k_node_evict, dim3((count + 255) / 256), dim3(256), 0, s, d_fit, d_own, count, N,
-                             reinterpret_cast<NodeEvict*>(d_row));
-      }
+      hipLaunchKernelGGL(k_bound_fit<true>, dim3((N + kSqTile - 1) / kSqTile), dim3(256), 0, s, I.cluster(), I.F,
+                         I.vstore.p, d_off, d_own, 1u, (BoundFit*)nullptr, reinterpret_cast<uint32_t*>(d_row));
+      return true;
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(I.hr_host, evict || per_node ? d_row : reinterpret_cast<uint8_t*>(d_fit), back_bytes,
-                          hipMemcpyDeviceToHost, s));
-    return stream_sync(I, s, err);
+    if (count)
+      hipLaunchKernelGGL(k_bound_fit_init, dim3((count + 255) / 256), dim3(256), 0, s, d_own, I.cluster().goff, count,
+                         d_fit);
+    sq_chunks(N, count, [&](uint32_t c0, uint32_t cn, dim3 grid) {
+      hipLaunchKernelGGL(k_bound_fit<false>, grid, dim3(256), 0, s, I.cluster(), I.F, I.vstore.p, d_off + c0, d_own + c0, cn,
+                         d_fit + c0, (uint32_t*)nullptr);
+    });
+    if (evict) {
+      HIPCHK(hipMemsetAsync(d_row, 0, row_bytes, s));
+      if (count)
+        hipLaunchKernelGGL(k_node_evict, dim3((count + 255) / 256), dim3(256), 0, s, d_fit, d_own, count, N,
+                           reinterpret_cast<NodeEvict*>(d_row));
+    }
+    return true;
   };
-  if (!run()) return KSG_E_DEVICE;
-  std::memcpy(per_node ? (void*)bo.codes : evict ? (void*)bo.evict : (void*)bo.fit, I.hr_host, back_bytes);
+  if (!sq_fetch(I, evict || per_node ? d_row : I.hr_dev.p, back_bytes, enqueue, err)) return KSG_E_DEVICE;
+  std::memcpy(per_node ? (void*)bo.codes : evict ? (void*)bo.evict : (void*)bo.fit, I.sq_host.p, back_bytes);
   return KSG_OK;
 }
 }  // namespace
-
-// host.cpp: the context's lock, guard, shard, profile and range checks, the
-// victim store ensured, then fn on the engine and the codes' positions translated
-int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, bool args_ok, const uint32_t* n_nodes,
-                   const char* what, BoundFitFn fn, const BoundFitOut& bo);
 
 }  // namespace ksg
 

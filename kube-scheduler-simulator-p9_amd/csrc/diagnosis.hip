@@ -24,8 +24,6 @@
 // (host.cpp diag_call) counts the kept filter row on the host instead.
 #include "../../include/ksg.h"
 
-struct ksg_ctx;
-
 namespace ksg {
 
 static_assert(kDiagMax == KSG_DIAG_MAX, "the device table holds KSG_DIAG_MAX slots");
@@ -122,7 +120,7 @@ int diag_counts(Engine& eng, uint32_t j, const Engine::ViewCfg& cfg, Engine::Dia
   auto run = [&]() -> bool {
     const uint32_t N = I.N, slots = I.diag_slots;
     if (!I.dg_tab.alloc(diag_bytes(kDiagMax), err)) return false;
-    if (!I.dg_host) HIPCHK(hipHostMalloc((void**)&I.dg_host, kDiagSumOff + sizeof(ksg_pod_summary), hipHostMallocDefault));
+    if (!I.sq_host.reserve(kDiagSumOff + sizeof(ksg_pod_summary), err)) return false;
     hipStream_t s = I.stream;
     const size_t bytes = diag_bytes(slots);
     HIPCHK(hipMemsetAsync(I.dg_tab.p, 0, bytes, s));
@@ -142,19 +140,19 @@ int diag_counts(Engine& eng, uint32_t j, const Engine::ViewCfg& cfg, Engine::Dia
                          reinterpret_cast<uint32_t*>(I.dg_tab.p));
       HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemcpyAsync(I.dg_host, I.dg_tab.p, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(I.dg_host + kDiagSumOff, I.sums.p + j, sizeof(ksg_pod_summary), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(I.sq_host.p, I.dg_tab.p, bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(I.sq_host.p + kDiagSumOff, I.sums.p + j, sizeof(ksg_pod_summary), hipMemcpyDeviceToHost, s));
     return stream_sync(I, s, err);
   };
   if (!run()) return KSG_E_DEVICE;
   const uint32_t slots = I.diag_slots;
-  std::memcpy(&out.summary, I.dg_host + kDiagSumOff, sizeof(out.summary));
+  std::memcpy(&out.summary, I.sq_host.p + kDiagSumOff, sizeof(out.summary));
   uint32_t over;
-  std::memcpy(&over, I.dg_host, sizeof(over));
+  std::memcpy(&over, I.sq_host.p, sizeof(over));
   out.overflow = over != 0;
   if (out.overflow) return KSG_OK;
-  const uint8_t* keys = I.dg_host + kDiagKeysOff;
-  const uint8_t* cnts = I.dg_host + diag_cnt_off(slots);
+  const uint8_t* keys = I.sq_host.p + kDiagKeysOff;
+  const uint8_t* cnts = I.sq_host.p + diag_cnt_off(slots);
   for (uint32_t t = 0; t < slots; ++t) {
     unsigned long long key;
     uint32_t cnt;
@@ -166,16 +164,6 @@ int diag_counts(Engine& eng, uint32_t j, const Engine::ViewCfg& cfg, Engine::Dia
   return KSG_OK;
 }
 }  // namespace
-
-// host.cpp: the context's lock, guard, range and shard checks, then count (the
-// device pass above) with the profile's view facts, the host count of the kept
-// filter row when the table overflowed, the order, and the answer the request
-// names (DiagRequest, engine.h): the buckets, or the FitError sentence rendered
-// from them
-int diag_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
-              int (*count)(Engine& eng, uint32_t prog, const Engine::ViewCfg& cfg, Engine::DiagCounts& out,
-                           std::string& err),
-              const DiagRequest& rq);
 
 }  // namespace ksg
 

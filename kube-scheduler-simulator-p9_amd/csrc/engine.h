@@ -13,6 +13,7 @@
 struct ksg_filter_bucket;  // include/ksg.h
 struct ksg_bound_fit;
 struct ksg_node_evict;
+struct ksg_ctx;
 
 namespace ksg {
 
@@ -366,5 +367,26 @@ struct BoundFitOut {
 };
 using BoundFitFn = int (*)(Engine& eng, uint32_t first, uint32_t count, const int32_t* own, const BoundFitOut& out,
                            std::string& err);
+
+// The context's side of the snapshot queries (host.cpp).  Their entry points live
+// in the engine's translation unit and hand the engine function over as a
+// pointer, so that host.cpp, which also links against a stand-in for the engine
+// (tests/fuzz), needs no new Engine member.  Each begins with snapshot_gate (lock,
+// guard, refusals, range) and runs fn on the engine; fn returns KSG_OK or a KSG_E*
+// code with its message in err, which becomes the context's last error.
+// ksg_ranked_nodes: fn gets q's program index (queue pod q is program q)
+int kept_pod_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
+                  int (*fn)(Engine& eng, uint32_t prog, void* user, std::string& err), void* user);
+// ksg_filter_histogram / ksg_fit_error: count is the device pass; the answer is the one rq names
+int diag_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
+              int (*count)(Engine& eng, uint32_t prog, const Engine::ViewCfg& cfg, Engine::DiagCounts& out,
+                           std::string& err),
+              const DiagRequest& rq);
+// ksg_headroom / ksg_headroom_nodes
+int headroom_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const uint32_t* n_nodes, const char* what,
+                  int (*fn)(Engine& eng, uint32_t first, uint32_t count, void* user, std::string& err), void* user);
+// ksg_bound_fit / ksg_bound_fit_nodes / ksg_node_evictability (whole: the range is every bound pod)
+int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, bool args_ok, const uint32_t* n_nodes,
+                   const char* what, BoundFitFn fn, const BoundFitOut& bo);
 
 }  // namespace ksg

@@ -5361,6 +5361,27 @@ struct DBuf {
   }
 };
 
+// A grow-only pinned host block (contents are not kept when it grows).  Engine::Impl::sq_host is the
+// one every snapshot query's answer crosses in (snapshot_query.hip): ranked candidates, the diagnosis,
+// headroom and the eviction fit share it, because the context's lock serialises the calls and each
+// unpacks its answer before it returns.
+struct PinnedBlock {
+  uint8_t* p = nullptr;
+  size_t cap = 0;
+  bool reserve(size_t bytes, std::string& err) {
+    if (bytes <= cap && p) return true;
+    if (p) HIPCHK(hipHostFree(p));
+    p = nullptr;
+    cap = 0;
+    HIPCHK(hipHostMalloc((void**)&p, bytes, hipHostMallocDefault));
+    cap = bytes;
+    return true;
+  }
+  ~PinnedBlock() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+
 // Engine::Impl::hverdict, the pinned host block of the persistent launches: word 0
 // is the handshake verdict, word kVerdictAbortWord Engine::sync's copy of the abort word
 constexpr size_t kVerdictBytes = 64;
@@ -5546,23 +5567,20 @@ struct Engine::Impl {
   uint32_t cnblk = 0;
   // ranked candidates (ranked.hip): nodes per block of the select (KSG_RANK_TILE: a power of two in
   // [128, kRankTile]; tests force the multi-level merge), the tiles' partial top lists (two levels,
-  // ping-pong; kept across calls, freed by release_scratch) and the pinned block the result crosses in
+  // ping-pong; kept across calls, freed by release_scratch)
   uint32_t rank_tile = kRankTile;
   DBuf<uint64_t> rk_part;
-  uint8_t* rk_host = nullptr;
   // unschedulable diagnosis (diagnosis.hip): slots of the device count table in use (KSG_DIAG_SLOTS: a
-  // power of two in [4, kDiagMax]; tests reach the overflow route with few reasons), the table (overflow
-  // word, keys, counts) and the pinned block it and the pod's summary cross in
+  // power of two in [4, kDiagMax]; tests reach the overflow route with few reasons) and the table (overflow
+  // word, keys, counts)
   uint32_t diag_slots = kDiagMax;
   DBuf<uint8_t> dg_tab;
-  uint8_t* dg_host = nullptr;
-  // headroom (headroom.hip): the device result structs (or one pod's node row) and the pinned block they cross in
+  // headroom (headroom.hip): the device result structs (or one pod's node row)
   DBuf<uint8_t> hr_dev;
-  uint8_t* hr_host = nullptr;
-  size_t hr_host_bytes = 0;
   // eviction fit (bound_fit.hip): a launch's inputs, the bound pods' store offsets and own nodes
-  // (its results use headroom's device and pinned blocks: the context lock serialises the calls)
+  // (its results use headroom's device block: the context lock serialises the calls)
   DBuf<uint8_t> bf_in;
+  PinnedBlock sq_host;  // the pinned block every snapshot query's answer crosses in
   DBuf<int32_t> knorm;   // normalized scores of one kept pod
   DBuf<uint8_t> vblk;     // device cycle view block (Engine::view)
   bool vblk_fresh = true;
@@ -5712,9 +5730,6 @@ Engine::~Engine() {
   if (p_->hverdict) (void)hipHostFree(p_->hverdict);
   if (p_->apstage) (void)hipHostFree(p_->apstage);
   if (p_->vstage) (void)hipHostFree(p_->vstage);
-  if (p_->rk_host) (void)hipHostFree(p_->rk_host);
-  if (p_->dg_host) (void)hipHostFree(p_->dg_host);
-  if (p_->hr_host) (void)hipHostFree(p_->hr_host);
   if (p_->apstage_ev) (void)hipEventDestroy(p_->apstage_ev);
   if (p_->ev0) (void)hipEventDestroy(p_->ev0);
   if (p_->ev1) (void)hipEventDestroy(p_->ev1);
@@ -8567,6 +8582,7 @@ extern "C" int ksg_debug_arith(int op, const int64_t* in, uint32_t cols, int64_t
   return rc;
 }
 
+#include "snapshot_query.hip"
 #include "ranked.hip"
 #include "diagnosis.hip"
 #include "headroom.hip"

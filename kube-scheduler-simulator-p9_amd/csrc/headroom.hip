@@ -3,18 +3,12 @@
 // device.  Part of the engine's translation unit (engine.hip includes it after
 // diagnosis.hip).
 //
-//   k_headroom<false>  a (node tile x pod tile) grid, as the what-if pass.  A block
-//                 of 256 threads owns kHrTile = 256 x kHrNpt nodes: every thread
-//                 loads its nodes' rows once, as free_r = allocatable_r -
-//                 requested_r for the R resource columns and room = max(0,
-//                 allowed - podcnt), and keeps them in registers.  It then walks
-//                 the kHrPods pods of its pod tile over them; the pods' program
-//                 headers and requests are wave-uniform reads through the scalar
-//                 cache.  The static filters are node_filter<kPmHeadroom>, the
-//                 switch every kernel shares (their per-node operands -- taints,
+//   k_headroom<false>  the (node tile x pod tile) grid of snapshot_query.hip
+//                 over the queue pods: the rows are sq_rows' with room = max(0,
+//                 left), the gate is sq_live, the static filters are
+//                 sq_walk<kPmHeadroom> (their per-node operands -- taints,
 //                 labels, the node flags -- are read there, from L1/L2 after the
-//                 tile's first pod); the reject flags and the PreFilterResult
-//                 bitmask as k_eval reads them.  The count is a running minimum:
+//                 tile's first pod).  The count is a running minimum:
 //                 it starts at the room and every requested column r lowers it to
 //                 div_cap(free_r, req_r, count), so the constraint that lowered it
 //                 last is the lowest index holding the minimum (bound[]).
@@ -31,23 +25,12 @@
 // in the place of the two fields; the host decodes it.  The answer does not
 // depend on the order in which waves and blocks arrive.
 //
-// Forward progress: no thread waits on another thread's progress (the one
-// barrier is reached by every thread of the block: the pod and node loops hold
-// no return), and every loop is bounded by a tile constant, the profile length
-// or KSG_MAX_RES.
-//
-// kHrTile = 1024 nodes and kHrPods = 32 pods: several node blocks per pod from
-// 1025 nodes, several pod tiles from 33 pods, so no override is read.
+// Forward progress: snapshot_query.hip's argument; the loops below hold no return.
 #include "../../include/ksg.h"
-
-struct ksg_ctx;
 
 namespace ksg {
 
 using Headroom = struct ::ksg_headroom;  // (the function of the same name hides the struct's)
-constexpr uint32_t kHrNpt = 4;              // nodes per thread
-constexpr uint32_t kHrTile = 256 * kHrNpt;  // nodes per block
-constexpr uint32_t kHrPods = 32;            // pods per block (grid.y tiles)
 constexpr uint32_t kHrWords = sizeof(Headroom) / 4;
 constexpr uint32_t kPmHeadroom = (1u << KP_TAINT) | (1u << KP_NA) | (1u << KP_UNSCHED) | (1u << KP_NODENAME);
 static_assert(KSG_HEADROOM_BOUNDS == 1 + KSG_MAX_RES, "bound[]: the pod room, then every resource column");
@@ -70,48 +53,32 @@ template <bool PER_NODE>
 __global__ __launch_bounds__(256) void k_headroom(DevCluster C, DevProfile F, const uint8_t* __restrict__ progs,
                                                   const uint64_t* __restrict__ prog_off, uint32_t q0, uint32_t count,
                                                   Headroom* out, int32_t* out_nodes) {
-  __shared__ __attribute__((aligned(16))) uint32_t acc[PER_NODE ? 1 : kHrPods * kHrWords];  // (64-bit words inside)
+  __shared__ __attribute__((aligned(16))) uint32_t acc[PER_NODE ? 1 : kSqPods * kHrWords];  // (64-bit words inside)
   if (!PER_NODE) {
-    for (uint32_t t = threadIdx.x; t < kHrPods * kHrWords; t += 256) acc[t] = 0;
+    for (uint32_t t = threadIdx.x; t < kSqPods * kHrWords; t += 256) acc[t] = 0;
     __syncthreads();
   }
   // the block's node rows, once
-  const uint32_t base = blockIdx.x * kHrTile + threadIdx.x;
-  int64_t fr[kHrNpt][KSG_MAX_RES];
-  int32_t room[kHrNpt];
+  const uint32_t base = blockIdx.x * kSqTile + threadIdx.x;
+  int64_t fr[kSqNpt][KSG_MAX_RES];
+  int32_t room[kSqNpt];
+  sq_rows(C, base, fr, room);
 #pragma unroll
-  for (uint32_t k = 0; k < kHrNpt; ++k) {
-    const uint32_t n = base + k * 256;
-    const bool live = n < C.N;
-    const int32_t left = live ? C.allowed[n] - C.podcnt[n] : 0;
-    room[k] = left > 0 ? left : 0;
-#pragma unroll
-    for (uint32_t r = 0; r < KSG_MAX_RES; ++r)
-      fr[k][r] = (live && r < C.R) ? C.alloc[(size_t)r * C.N + n] - C.req[(size_t)r * C.N + n] : 0;
-  }
+  for (uint32_t k = 0; k < kSqNpt; ++k) room[k] = room[k] > 0 ? room[k] : 0;
 #pragma unroll 1
-  for (uint32_t pi = 0; pi < kHrPods; ++pi) {
-    const uint32_t j = blockIdx.y * kHrPods + pi;
+  for (uint32_t pi = 0; pi < kSqPods; ++pi) {
+    const uint32_t j = blockIdx.y * kSqPods + pi;
     if (j >= count) break;  // (block-uniform)
     const ProgView V = view(progs + prog_off[q0 + j]);
     const ksg_prog* h = V.h;
     const uint32_t flags = h->flags;
-    const bool rejected = (flags & (KPF_PREFILTER_REJECT | KPF_PREFILTER_ERROR)) != 0;
-    bool open[kHrNpt];
-    int32_t cnt[kHrNpt];
-    uint32_t which[kHrNpt];
+    bool open[kSqNpt];
+    int32_t cnt[kSqNpt];
+    uint32_t which[kSqNpt];
 #pragma unroll
-    for (uint32_t k = 0; k < kHrNpt; ++k) {
+    for (uint32_t k = 0; k < kSqNpt; ++k) {
       const uint32_t n = base + k * 256;
-      bool ok = n < C.N && !rejected &&
-                !((flags & KPF_RESTRICT) && !bit(V.u32 + h->restrict_off, h->restrict_words, (int32_t)n));
-      if (ok) {
-        uint32_t code = KSG_FILTER_PASS;
-#pragma unroll 1
-        for (int pos = 0; pos < F.n && code == KSG_FILTER_PASS; ++pos)
-          code = node_filter<kPmHeadroom>(F.plugins[pos], pos, C, V, n);
-        ok = code == KSG_FILTER_PASS;
-      }
+      const bool ok = sq_live(C, V, n) && sq_walk<kPmHeadroom>(C, F, V, n) == KSG_FILTER_PASS;
       open[k] = ok;
       cnt[k] = ok ? room[k] : 0;
       which[k] = 0;
@@ -122,7 +89,7 @@ __global__ __launch_bounds__(256) void k_headroom(DevCluster C, DevProfile F, co
         const int64_t rq = h->req[r];
         if (r >= C.R || rq <= 0) continue;  // (wave-uniform)
 #pragma unroll
-        for (uint32_t k = 0; k < kHrNpt; ++k) {
+        for (uint32_t k = 0; k < kSqNpt; ++k) {
           if (!open[k]) continue;
           const int64_t f = fr[k][r];
           const int32_t fit = f < 0 ? 0 : (int32_t)div_cap(f, rq, cnt[k]);
@@ -135,7 +102,7 @@ __global__ __launch_bounds__(256) void k_headroom(DevCluster C, DevProfile F, co
     }
     if (PER_NODE) {
 #pragma unroll
-      for (uint32_t k = 0; k < kHrNpt; ++k) {
+      for (uint32_t k = 0; k < kSqNpt; ++k) {
         const uint32_t n = base + k * 256;
         if (n < C.N) out_nodes[n] = cnt[k];
       }
@@ -145,7 +112,7 @@ __global__ __launch_bounds__(256) void k_headroom(DevCluster C, DevProfile F, co
     uint64_t sum = 0, key = 0;
     uint32_t n_pos = 0, n_open = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < kHrNpt; ++k) {
+    for (uint32_t k = 0; k < kSqNpt; ++k) {
       sum += (uint32_t)cnt[k];
       const uint64_t kk = ((uint64_t)(uint32_t)cnt[k] << 32) | (0xFFFFFFFFu - (C.goff + base + k * 256));
       if (cnt[k] > 0 && kk > key) key = kk;
@@ -167,17 +134,17 @@ __global__ __launch_bounds__(256) void k_headroom(DevCluster C, DevProfile F, co
     for (uint32_t i = 0; i < 1 + C.R; ++i) {  // (R <= KSG_MAX_RES: the columns the cluster has)
       uint32_t c = 0;
 #pragma unroll
-      for (uint32_t k = 0; k < kHrNpt; ++k) c += (uint32_t)__popcll(__ballot(open[k] && which[k] == i));
+      for (uint32_t k = 0; k < kSqNpt; ++k) c += (uint32_t)__popcll(__ballot(open[k] && which[k] == i));
       if (c && lane0()) atomicAdd(a + kHrwBound + i, c);
     }
   }
   if (PER_NODE) return;
   __syncthreads();
   // one global atomic per block and non-zero field
-  const uint32_t pods = count - blockIdx.y * kHrPods < kHrPods ? count - blockIdx.y * kHrPods : kHrPods;
+  const uint32_t pods = count - blockIdx.y * kSqPods < kSqPods ? count - blockIdx.y * kSqPods : kSqPods;
   for (uint32_t t = threadIdx.x; t < pods * kHrWords; t += 256) {
     const uint32_t pi = t / kHrWords, w = t % kHrWords;
-    uint32_t* g = reinterpret_cast<uint32_t*>(out + (size_t)blockIdx.y * kHrPods + pi) + w;
+    uint32_t* g = reinterpret_cast<uint32_t*>(out + (size_t)blockIdx.y * kSqPods + pi) + w;
     const uint32_t* a = acc + pi * kHrWords + w;
     if (w == kHrwReplicas || w == kHrwKey) {
       const unsigned long long v = *reinterpret_cast<const unsigned long long*>(a);
@@ -191,9 +158,6 @@ __global__ __launch_bounds__(256) void k_headroom(DevCluster C, DevProfile F, co
 }
 
 namespace {
-// one launch covers at most this many pods (grid.y <= 65535)
-constexpr uint32_t kHrLaunchPods = 65535u * kHrPods;
-
 struct HeadroomCall {
   Headroom* out;       // ksg_headroom: count structs
   int32_t* out_nodes;  // ksg_headroom_nodes: N counts of pod `first`
@@ -211,41 +175,27 @@ int headroom_run(Engine& eng, uint32_t first, uint32_t count, void* user, std::s
   }
   const size_t bytes = per_node ? (size_t)N * sizeof(int32_t) : (size_t)count * sizeof(Headroom);
   if (!bytes) return KSG_OK;
-  auto run = [&]() -> bool {
-    if (!I.hr_dev.alloc(bytes, err)) return false;
-    if (I.hr_host_bytes < bytes) {
-      if (I.hr_host) HIPCHK(hipHostFree(I.hr_host));
-      I.hr_host = nullptr;
-      I.hr_host_bytes = 0;
-      HIPCHK(hipHostMalloc((void**)&I.hr_host, bytes, hipHostMallocDefault));
-      I.hr_host_bytes = bytes;
-    }
-    hipStream_t s = I.stream;
-    const uint32_t tiles = (N + kHrTile - 1) / kHrTile;
+  auto enqueue = [&](hipStream_t s) -> bool {
     if (per_node) {
-      hipLaunchKernelGGL(k_headroom<true>, dim3(tiles), dim3(256), 0, s, I.cluster(), I.F, I.progs.p, I.prog_off_d.p, first,
-                         1u, (Headroom*)nullptr, reinterpret_cast<int32_t*>(I.hr_dev.p));
-    } else {
-      HIPCHK(hipMemsetAsync(I.hr_dev.p, 0, bytes, s));
-      for (uint32_t c0 = 0; tiles && c0 < count; c0 += kHrLaunchPods) {
-        const uint32_t cn = std::min(count - c0, kHrLaunchPods);
-        hipLaunchKernelGGL(k_headroom<false>, dim3(tiles, (cn + kHrPods - 1) / kHrPods), dim3(256), 0, s, I.cluster(), I.F,
-                           I.progs.p, I.prog_off_d.p, first + c0, cn, reinterpret_cast<Headroom*>(I.hr_dev.p) + c0,
-                           (int32_t*)nullptr);
-      }
+      hipLaunchKernelGGL(k_headroom<true>, dim3((N + kSqTile - 1) / kSqTile), dim3(256), 0, s, I.cluster(), I.F, I.progs.p,
+                         I.prog_off_d.p, first, 1u, (Headroom*)nullptr, reinterpret_cast<int32_t*>(I.hr_dev.p));
+      return true;
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(I.hr_host, I.hr_dev.p, bytes, hipMemcpyDeviceToHost, s));
-    return stream_sync(I, s, err);
+    HIPCHK(hipMemsetAsync(I.hr_dev.p, 0, bytes, s));
+    sq_chunks(N, count, [&](uint32_t c0, uint32_t cn, dim3 grid) {
+      hipLaunchKernelGGL(k_headroom<false>, grid, dim3(256), 0, s, I.cluster(), I.F, I.progs.p, I.prog_off_d.p, first + c0,
+                         cn, reinterpret_cast<Headroom*>(I.hr_dev.p) + c0, (int32_t*)nullptr);
+    });
+    return true;
   };
-  if (!run()) return KSG_E_DEVICE;
+  if (!I.hr_dev.alloc(bytes, err) || !sq_fetch(I, I.hr_dev.p, bytes, enqueue, err)) return KSG_E_DEVICE;
   if (per_node) {
-    std::memcpy(hc.out_nodes, I.hr_host, bytes);
+    std::memcpy(hc.out_nodes, I.sq_host.p, bytes);
     return KSG_OK;
   }
   for (uint32_t i = 0; i < count; ++i) {  // the key back into its two fields
     Headroom hr;
-    std::memcpy(&hr, I.hr_host + (size_t)i * sizeof(hr), sizeof(hr));
+    std::memcpy(&hr, I.sq_host.p + (size_t)i * sizeof(hr), sizeof(hr));
     uint64_t key;
     std::memcpy(&key, reinterpret_cast<const uint8_t*>(&hr) + kHrwKey * 4, sizeof(key));
     hr.max_node = (int32_t)(key >> 32);
@@ -255,11 +205,6 @@ int headroom_run(Engine& eng, uint32_t first, uint32_t count, void* user, std::s
   return KSG_OK;
 }
 }  // namespace
-
-// host.cpp: the context's lock, guard, shard, profile and range checks, the
-// programs of the range compiled if they are not yet, then fn on the engine
-int headroom_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const uint32_t* n_nodes, const char* what,
-                  int (*fn)(Engine& eng, uint32_t first, uint32_t count, void* user, std::string& err), void* user);
 
 }  // namespace ksg
 

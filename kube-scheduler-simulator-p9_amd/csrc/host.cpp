@@ -4437,6 +4437,11 @@ struct Cluster {
   uint32_t code_detail(uint32_t code) const {
     return is_volume(plugins[fpos[code >> 24]]) ? code & 0xFFFFu : code & 0xFFFFFFu;
   }
+  // a device filter code as the API reports it: its position the profile's (KSG_FILTER_PASS and
+  // KSG_FILTER_NOT_EVALUATED as they are)
+  uint32_t profile_code(uint32_t code) const {
+    return code >= KSG_FILTER_NOT_EVALUATED ? code : ((uint32_t)code_pos(code) << 24) | code_detail(code);
+  }
   uint32_t skip_score_mask(const PodMeta& m, const ksg_pod_summary& S) const {
     uint32_t skip_s = 0;
     if (m.flags & KPF_SKIP_NA_SCORE) skip_s |= 1u << P_NA;
@@ -4817,6 +4822,8 @@ struct ksg_ctx {
     t_err_own = true;
     return code;
   }
+  // the tail of a call into the engine: rc with the engine's message (c.err) as the last error
+  int done(int rc) { return rc == KSG_OK ? KSG_OK : fail(c.err, rc); }
 };
 namespace ksg {
 bool rccl_selftest(int device, size_t bytes, std::string& err);  // engine.hip (diagnostic)
@@ -5076,10 +5083,7 @@ int ksg_filter_codes(ksg_ctx* ctx, uint32_t q, uint32_t* out, uint32_t n) {
   ksg::PodOutputs o;
   if (!ctx->c.eng->outputs(q, o, ctx->c.err)) return ctx->fail(ctx->c.err, KSG_E_STATE);
   if (n < o.filter.size()) return KSG_E_NOBUF;
-  for (size_t i = 0; i < o.filter.size(); ++i) {  // device position -> profile position
-    uint32_t c = o.filter[i];
-    out[i] = c >= KSG_FILTER_NOT_EVALUATED ? c : ((uint32_t)ctx->c.code_pos(c) << 24) | ctx->c.code_detail(c);
-  }
+  for (size_t i = 0; i < o.filter.size(); ++i) out[i] = ctx->c.profile_code(o.filter[i]);
   return KSG_OK;
 }
 
@@ -5669,42 +5673,55 @@ int ksg_node_nonzero(ksg_ctx* ctx, int64_t* nonzero, uint32_t n) {
 
 }  // extern "C"
 
-// The context's side of a lookup whose entry point lives in the engine's
-// translation unit (ksg_ranked_nodes, csrc/ranked.hip), so that this file, which
-// also links against a stand-in for the engine (tests/fuzz), needs no new Engine
-// member: the lock, the guard, the argument / queue-range check (KSG_E_RANGE), the
-// refusal of sharded contexts (KSG_E_INVALID), then fn on the engine with q's
-// program index (queue pod q is program q).  fn returns KSG_OK or a KSG_E* code
-// with its message in err, which becomes the context's last error.
+// The context's side of the snapshot queries (engine.h: kept_pod_call, diag_call,
+// headroom_call, bound_fit_call; DESIGN.md "Snapshot queries").
 namespace ksg {
+namespace {
+enum : int {
+  kGateRangeFirst = 1,  // ksg_ranked_nodes: an out-of-range q on a sharded context answers KSG_E_RANGE
+  kGateClosedForm = 2,  // refuse a profile outside headroom's closed form
+};
+// What every snapshot query begins with: the lock (held in lk from here on), the
+// guard, then in this order the refusal of sharded contexts and of a profile
+// outside the closed form (KSG_E_INVALID), and the argument / range check: pods
+// [.., end) against limit(c) and, with n_nodes, the caller's node count against
+// the local one (KSG_E_RANGE).  what: the entry point's name.  KSG_OK: go on.
+int snapshot_gate(ksg_ctx* ctx, std::unique_lock<std::recursive_mutex>& lk, const char* what, int checks, bool args_ok,
+                  uint64_t end, size_t (*limit)(const Cluster& c), const uint32_t* n_nodes = nullptr) {
+  if (ctx) lk = std::unique_lock<std::recursive_mutex>(ctx->mu);
+  KSG_GUARD(ctx);
+  const Cluster& c = ctx->c;
+  const bool in_range = args_ok && end <= limit(c) && (!n_nodes || *n_nodes == c.hi - c.lo);
+  if ((checks & kGateRangeFirst) && !in_range) return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
+  if (c.shards > 1) return ctx->fail(std::string(what) + ": not offered on a sharded context", KSG_E_INVALID);
+  if ((checks & kGateClosedForm) && !c.headroom_refusal.empty())
+    return ctx->fail(std::string(what) + ": " + c.headroom_refusal, KSG_E_INVALID);
+  if (!in_range) return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
+  return KSG_OK;
+}
+size_t kept_limit(const Cluster& c) { return std::min(c.queue.size(), c.meta.size()); }
+}  // namespace
+
 int kept_pod_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
                   int (*fn)(Engine& eng, uint32_t prog, void* user, std::string& err), void* user) {
-  KSG_LOCK(ctx);
-  KSG_GUARD(ctx);
+  std::unique_lock<std::recursive_mutex> lk;
+  if (const int rc = snapshot_gate(ctx, lk, what, kGateRangeFirst, args_ok, (uint64_t)q + 1, kept_limit)) return rc;
   auto& c = ctx->c;
-  if (!args_ok || q >= c.queue.size() || q >= c.meta.size()) return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
-  if (c.shards > 1) return ctx->fail(std::string(what) + ": not offered on a sharded context", KSG_E_INVALID);
-  const int rc = fn(*c.eng, q, user, c.err);
-  return rc == KSG_OK ? KSG_OK : ctx->fail(c.err, rc);
+  return ctx->done(fn(*c.eng, q, user, c.err));
 }
 
-// The same for the unschedulable diagnosis (ksg_filter_histogram / ksg_fit_error,
-// csrc/diagnosis.hip), whose answer also needs the object model: count is the
-// engine's device pass over q's kept filter row; when its table overflowed the
-// row is counted here, from the kept outputs; then the order, the positions and
-// (text) the messages, all under the one lock.
+// The diagnosis' answer also needs the object model: when the device table
+// overflowed the row is counted here, from the kept outputs; then the order, the
+// positions and (text) the messages, all under the one lock.
 int diag_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
               int (*count)(Engine& eng, uint32_t prog, const Engine::ViewCfg& cfg, Engine::DiagCounts& out,
                            std::string& err),
               const DiagRequest& rq) {
-  KSG_LOCK(ctx);
-  KSG_GUARD(ctx);
+  std::unique_lock<std::recursive_mutex> lk;
+  if (const int rc = snapshot_gate(ctx, lk, what, 0, args_ok, (uint64_t)q + 1, kept_limit)) return rc;
   auto& c = ctx->c;
-  if (c.shards > 1) return ctx->fail(std::string(what) + ": not offered on a sharded context", KSG_E_INVALID);
-  if (!args_ok || q >= c.queue.size() || q >= c.meta.size()) return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
   Engine::DiagCounts dc;
-  const int rc = count(*c.eng, q, c.view_cfg(), dc, c.err);
-  if (rc != KSG_OK) return ctx->fail(c.err, rc);
+  if (const int rc = count(*c.eng, q, c.view_cfg(), dc, c.err)) return ctx->fail(c.err, rc);
   if (dc.overflow && !c.diag_host_counts(q, dc.entries)) return ctx->fail(c.err, KSG_E_STATE);
   c.diag_routes[dc.overflow ? 1 : 0]++;
   if (rq.text) {
@@ -5715,15 +5732,12 @@ int diag_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
     std::memcpy(rq.buf, s.data(), s.size());
     return KSG_OK;
   }
-  // the codes as ksg_filter_codes reports them (device position -> profile position), in order
+  // the codes as ksg_filter_codes reports them, in order
   std::map<std::pair<uint32_t, int32_t>, ksg_filter_bucket> buckets;
   for (const Engine::DiagEntry& e : dc.entries) {
-    ksg_filter_bucket b{e.code, -1, e.status, 0};
+    ksg_filter_bucket b{c.profile_code(e.code), -1, e.status, 0};
     if (e.code == KSG_FILTER_PASS) b.pos = c.n_plugins;
-    else if (e.code != KSG_FILTER_NOT_EVALUATED) {
-      b.pos = c.code_pos(e.code);
-      b.code = ((uint32_t)b.pos << 24) | c.code_detail(e.code);
-    }
+    else if (e.code != KSG_FILTER_NOT_EVALUATED) b.pos = c.code_pos(e.code);
     auto it = buckets.emplace(std::make_pair(b.code, b.status), b).first;
     it->second.count += e.count;
   }
@@ -5733,67 +5747,48 @@ int diag_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
   for (auto& kv : buckets) rq.out[i++] = kv.second;
   return KSG_OK;
 }
-}  // namespace ksg
 
-namespace ksg {
-// The same for headroom (ksg_headroom / ksg_headroom_nodes, csrc/headroom.hip): the
-// lock, the guard, the refusals (a sharded context, a profile outside the closed
-// form: KSG_E_INVALID), the argument / queue-range check and, with n_nodes, the
-// caller's node count against the local one (KSG_E_RANGE); the queue's programs
-// compiled if they are not yet (as ksg_whatif); then fn on the engine.
+// Headroom: the queue's programs compiled if they are not yet (as ksg_whatif).
 int headroom_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const uint32_t* n_nodes, const char* what,
                   int (*fn)(Engine& eng, uint32_t first, uint32_t count, void* user, std::string& err), void* user) {
-  KSG_LOCK(ctx);
-  KSG_GUARD(ctx);
+  std::unique_lock<std::recursive_mutex> lk;
+  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, (uint64_t)first + count,
+                                   [](const Cluster& c) { return c.queue.size(); }, n_nodes))
+    return rc;
   auto& c = ctx->c;
-  if (c.shards > 1) return ctx->fail(std::string(what) + ": not offered on a sharded context", KSG_E_INVALID);
-  if (!c.headroom_refusal.empty()) return ctx->fail(std::string(what) + ": " + c.headroom_refusal, KSG_E_INVALID);
-  if (!args_ok || (uint64_t)first + count > c.queue.size() || (n_nodes && *n_nodes != c.hi - c.lo))
-    return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
   if (!count) return KSG_OK;
   if (!c.compile_queue()) return ctx->fail(c.err, KSG_E_INVALID);
   if (!c.refresh_programs(first, count)) return ctx->fail(c.err, KSG_E_DEVICE);
-  const int rc = fn(*c.eng, first, count, user, c.err);
-  return rc == KSG_OK ? KSG_OK : ctx->fail(c.err, rc);
+  return ctx->done(fn(*c.eng, first, count, user, c.err));
 }
-}  // namespace ksg
 
-namespace ksg {
-// The same for the eviction fit (ksg_bound_fit / ksg_bound_fit_nodes /
-// ksg_node_evictability, csrc/bound_fit.hip): the lock, the guard, headroom's
-// refusals (under its profiles removing a bound pod changes its own node's rows
-// only), the argument / bound-range check and, with n_nodes, the caller's node
-// count against the local one (KSG_E_RANGE); whole: the range is every bound pod.
+// The eviction fit: headroom's refusals (under its profiles removing a bound pod
+// changes its own node's rows only); whole: the range is every bound pod (the
+// gate sees it as the empty range, which is in range whenever the whole is).
 // The victim store is ensured whether or not DefaultPreemption is in the
 // profile: per snapshot generation the first call compiles every bound pod's
 // program (the queue's classes first: the store is built against them).  Then
 // fn on the engine, and the codes from device to profile positions.
 int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, bool args_ok, const uint32_t* n_nodes,
                    const char* what, BoundFitFn fn, const BoundFitOut& bo) {
-  KSG_LOCK(ctx);
-  KSG_GUARD(ctx);
+  std::unique_lock<std::recursive_mutex> lk;
+  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, whole ? 0 : (uint64_t)first + count,
+                                   [](const Cluster& c) { return c.bound.size(); }, n_nodes))
+    return rc;
   auto& c = ctx->c;
-  if (c.shards > 1) return ctx->fail(std::string(what) + ": not offered on a sharded context", KSG_E_INVALID);
-  if (!c.headroom_refusal.empty()) return ctx->fail(std::string(what) + ": " + c.headroom_refusal, KSG_E_INVALID);
   if (whole) {
     first = 0;
     count = (uint32_t)c.bound.size();
   }
-  if (!args_ok || (uint64_t)first + count > c.bound.size() || (n_nodes && *n_nodes != c.hi - c.lo))
-    return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
   if (!count && !whole) return KSG_OK;
   if (!c.compile_queue()) return ctx->fail(c.err, KSG_E_INVALID);
   if (!c.ensure_victim_store()) return ctx->fail(c.err, KSG_E_DEVICE);
   const std::vector<int32_t>& own = c.bound_own_nodes();
-  const int rc = fn(*c.eng, first, count, own.data(), bo, c.err);
-  if (rc != KSG_OK) return ctx->fail(c.err, rc);
-  auto profile_code = [&](uint32_t code) {
-    return code >= KSG_FILTER_NOT_EVALUATED ? code : ((uint32_t)c.code_pos(code) << 24) | c.code_detail(code);
-  };
+  if (const int rc = fn(*c.eng, first, count, own.data(), bo, c.err)) return ctx->fail(c.err, rc);
   if (bo.fit)
-    for (uint32_t i = 0; i < count; ++i) bo.fit[i].own_code = profile_code(bo.fit[i].own_code);
+    for (uint32_t i = 0; i < count; ++i) bo.fit[i].own_code = c.profile_code(bo.fit[i].own_code);
   if (bo.codes)
-    for (uint32_t i = 0; i < c.hi - c.lo; ++i) bo.codes[i] = profile_code(bo.codes[i]);
+    for (uint32_t i = 0; i < c.hi - c.lo; ++i) bo.codes[i] = c.profile_code(bo.codes[i]);
   return KSG_OK;
 }
 }  // namespace ksg

@@ -15,8 +15,6 @@
 // the pod's summary through a pinned block and unpacks node and total.
 #include "../../include/ksg.h"
 
-struct ksg_ctx;
-
 namespace ksg {
 
 static_assert(kRankTile >= 2 * KSG_RANK_MAX, "a tile holds two partial lists: every merge level shrinks");
@@ -103,7 +101,7 @@ bool rank_keys(Engine::Impl& I, uint32_t j, uint32_t k, std::string& err) {
   const size_t n_a = (size_t)tiles * KSG_RANK_MAX;
   const size_t n_b = (n_a + tile - 1) / tile * KSG_RANK_MAX;
   if (!I.rk_part.alloc(std::max<size_t>(n_a + n_b, KSG_RANK_MAX), err)) return false;
-  if (!I.rk_host) HIPCHK(hipHostMalloc((void**)&I.rk_host, kRankKeyBytes + sizeof(ksg_pod_summary), hipHostMallocDefault));
+  if (!I.sq_host.reserve(kRankKeyBytes + sizeof(ksg_pod_summary), err)) return false;
   hipStream_t s = I.stream;
   uint64_t *a = I.rk_part.p, *b = I.rk_part.p + n_a;
   if (tiles) {
@@ -117,9 +115,9 @@ bool rank_keys(Engine::Impl& I, uint32_t j, uint32_t k, std::string& err) {
       m = nb;
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(I.rk_host, a, k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(I.sq_host.p, a, k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   }
-  HIPCHK(hipMemcpyAsync(I.rk_host + kRankKeyBytes, I.sums.p + j, sizeof(ksg_pod_summary), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(I.sq_host.p + kRankKeyBytes, I.sums.p + j, sizeof(ksg_pod_summary), hipMemcpyDeviceToHost, s));
   return stream_sync(I, s, err);
 }
 
@@ -137,7 +135,7 @@ int rank_call(Engine& eng, uint32_t j, void* user, std::string& err) {
   }
   if (!rank_keys(I, j, rc.k, err)) return KSG_E_DEVICE;
   ksg_pod_summary sum;
-  std::memcpy(&sum, I.rk_host + kRankKeyBytes, sizeof(sum));
+  std::memcpy(&sum, I.sq_host.p + kRankKeyBytes, sizeof(sum));
   if (sum.status != 0 || sum.feasible <= 0 || !I.N) return KSG_OK;  // unschedulable, or the cycle ended in an error
   if (sum.feasible == 1) {  // upstream's shortcut: no scoring, the summary holds the node and its total
     rc.out[0].node = sum.selected;
@@ -146,7 +144,7 @@ int rank_call(Engine& eng, uint32_t j, void* user, std::string& err) {
     return KSG_OK;
   }
   const uint32_t n = std::min<uint32_t>(rc.k, (uint32_t)sum.feasible);
-  const uint64_t* keys = reinterpret_cast<const uint64_t*>(I.rk_host);
+  const uint64_t* keys = reinterpret_cast<const uint64_t*>(I.sq_host.p);
   for (uint32_t i = 0; i < n; ++i) {
     if (!keys[i]) {
       err = "ranked_nodes: the pod's kept outputs hold fewer feasible nodes than its summary";
@@ -159,10 +157,6 @@ int rank_call(Engine& eng, uint32_t j, void* user, std::string& err) {
   return KSG_OK;
 }
 }  // namespace
-
-// host.cpp: the context's lock, guard, range and shard checks around fn
-int kept_pod_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
-                  int (*fn)(Engine& eng, uint32_t prog, void* user, std::string& err), void* user);
 
 }  // namespace ksg
 

@@ -10,8 +10,8 @@ and hand-written literals, pinned against each other there on the CPU; and, on
 the GPU, the engine's existing route (removePod, ksg_cycle(commit=0),
 ksg_filter_codes, addPod), code for code.
 
-Kernel constants (csrc/bound_fit.hip): a block of 256 threads owns kBfTile = 1024
-nodes (4 per thread) and walks kBfPods = 32 bound pods over them.
+Kernel constants (csrc/snapshot_query.hip): a block of 256 threads owns kSqTile = 1024
+nodes (4 per thread) and walks kSqPods = 32 bound pods over them.
 """
 import copy
 import ctypes

@@ -8,8 +8,8 @@ copies scheduled; every fill asserts that a copy was left over) and a few lines
 of Python integers over the document, pinned there against the fill and against
 hand-written literals.
 
-Kernel constants (csrc/headroom.hip): a block of 256 threads owns kHrTile = 1024
-nodes (kHrNpt = 4 per thread) and walks kHrPods = 32 pods over them; several
+Kernel constants (csrc/snapshot_query.hip): a block of 256 threads owns kSqTile = 1024
+nodes (kSqNpt = 4 per thread) and walks kSqPods = 32 pods over them; several
 node blocks per pod start at 1025 nodes and several pod tiles at 33 pods, so no
 tile override exists.
 """
@@ -81,7 +81,7 @@ def test_families(family):
 # ------------------------------------------------------------------ 3: tile edges
 @pytest.mark.parametrize("n_nodes", [TILE - 1, TILE, TILE + 1, 2 * TILE + 52])
 def test_node_tile_edges(n_nodes):
-    """kHrTile = 1024 nodes a block: one node short, exact, one node into a second block, and two blocks
+    """kSqTile = 1024 nodes a block: one node short, exact, one node into a second block, and two blocks
     plus a ragged third; POD_TILE + 1 pods, so the second pod tile holds one pod."""
     doc = m.tile_doc(n_nodes, POD_TILE + 1)
     s = load(doc)
@@ -92,7 +92,7 @@ def test_node_tile_edges(n_nodes):
 
 @pytest.mark.parametrize("n_pods", [1, POD_TILE - 1, POD_TILE, POD_TILE + 1])
 def test_pod_tile_edges(n_pods):
-    """kHrPods = 32 pods a block, over two node blocks (1025 nodes); sub-ranges start inside a tile."""
+    """kSqPods = 32 pods a block, over two node blocks (1025 nodes); sub-ranges start inside a tile."""
     doc = m.tile_doc(TILE + 1, n_pods)
     s = load(doc)
     got = check_all(s, doc, rows_of={0, n_pods - 1})
