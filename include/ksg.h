@@ -53,7 +53,8 @@ extern "C" {
  * ksg_filter_bucket, KSG_DIAG_MAX; ksg_headroom (the call and the struct),
  * ksg_headroom_nodes, ksg_resource_name, KSG_HEADROOM_BOUNDS; ksg_bound_count,
  * ksg_bound_pod, ksg_bound_fit (the call and the struct), ksg_bound_fit_nodes,
- * ksg_node_evictability, ksg_node_evict. */
+ * ksg_node_evictability, ksg_node_evict; ksg_drain (the call and the struct),
+ * ksg_drain_plan, ksg_drain_move, KSG_DRAIN_MAX. */
 #define KSG_ABI_VERSION 4
 
 #define KSG_OK 0
@@ -472,6 +473,63 @@ struct ksg_node_evict {         /* 16 bytes, per local node */
   int32_t reserved;  /* 0 */
 };
 int ksg_node_evictability(ksg_ctx* ctx, struct ksg_node_evict* out, uint32_t n);
+
+/* Drain simulation (the cluster-autoscaler's scale-down simulation, the planning
+ * of a `kubectl drain`): can local node x be emptied -- its pods re-placed one
+ * after another, each counted on its new node before the next is judged.  Where
+ * ksg_node_evictability gives the necessary condition, this is the sufficient
+ * one for the order it simulates.  One block per candidate on the device
+ * (csrc/drain.hip), every candidate of a call in one launch.
+ * Subjects.  The bound pods on x (the bound list of the eviction fit above) in
+ * ascending bound index, except the pods a drain leaves in place: pods whose
+ * controller owner reference has kind DaemonSet, and mirror pods (annotation
+ * kubernetes.io/config.mirror), as `kubectl drain --ignore-daemonsets` and the
+ * autoscaler leave them.  They are counted in `daemon` and stay on x.  Queue
+ * pods placed since the last encode are load, not subjects, as above.
+ * The simulation runs against the device snapshot as it stands when the call
+ * runs (every assume, Reserve and event applied so far).  For subject b, in
+ * order, dest(b) is the lowest global node index n != x whose code is
+ * KSG_FILTER_PASSED, the code being that of ksg_bound_fit_nodes (NodeName's
+ * Filter is not applied) with this drain's earlier placements counted:
+ * NodeResourcesFit reads requested_r(n) plus the sum of request_r(b') over the
+ * earlier subjects b' with dest(b') == n, and pod count(n) plus the number of
+ * those subjects.  x itself is never a destination.  A subject with no such node
+ * is unplaced, and the simulation goes on with the next subject.  Every
+ * candidate's drain is independent of every other candidate's; nothing is moved
+ * and no scheduling state changes.
+ * First fit in node order is deliberate: it is deterministic, needs no Score, and
+ * is what a scale-down simulation does.  It is not the scheduler's choice: a real
+ * cycle scores the feasible nodes and selectHost picks among the best, so the
+ * pods of a real drain may land elsewhere.  The answer says that a placement
+ * exists for this order, not which one the scheduler will make.
+ * At most KSG_DRAIN_MAX subjects are simulated per candidate; further subjects are
+ * counted in `skipped` (dest -2 in the plan) and the drain is then not complete.
+ * A node is drainable when unplaced == 0 && skipped == 0.  (Environment
+ * KSG_DRAIN_MAX, read at ksg_create: a power of two in [2, 512] that lowers the
+ * cap; tests reach it with a handful of pods.)
+ * ksg_drain fills out[i] for local nodes [first_node, first_node + count).
+ * ksg_drain_plan returns the subjects of one local node in simulation order with
+ * their destinations; buffer convention of ksg_filter_histogram: *n_out receives
+ * the number of subjects, cap too small: KSG_E_NOBUF with the needed count.
+ * Profiles, refusals and errors are those of ksg_bound_fit: a profile outside
+ * headroom's closed form or a sharded context: KSG_E_INVALID; out (or n_out) NULL,
+ * the range outside the local nodes: KSG_E_RANGE; count == 0: KSG_OK, nothing
+ * written.  Two calls return the same bytes.  Indices in the answer are host bound
+ * indices and global node indices. */
+#define KSG_DRAIN_MAX 512
+struct ksg_drain {            /* 32 bytes, per candidate node */
+  int32_t pods;            /* bound pods on the node */
+  int32_t daemon;          /* of them, DaemonSet-owned or mirror pods: left in place */
+  int32_t placed;          /* subjects that found a destination */
+  int32_t unplaced;        /* subjects that found none */
+  int32_t skipped;         /* subjects beyond KSG_DRAIN_MAX: not simulated */
+  int32_t first_unplaced;  /* bound index of the first unplaced subject, -1 when none */
+  int32_t dest_nodes;      /* distinct destination nodes */
+  int32_t reserved;        /* 0 */
+};                          /* drainable: unplaced == 0 && skipped == 0 */
+struct ksg_drain_move { int32_t bound; int32_t dest; };  /* dest: global node, -1 unplaced, -2 skipped */
+int ksg_drain(ksg_ctx* ctx, uint32_t first_node, uint32_t count, struct ksg_drain* out);
+int ksg_drain_plan(ksg_ctx* ctx, uint32_t node, struct ksg_drain_move* out, uint32_t cap, uint32_t* n_out);
 
 /* PostFilter (wrappedplugin.go:550-577 -> store.go:442 AddPostFilterResult):
  * DefaultPreemption's dry run for an unschedulable pod q (PodEligibleToPreemptOthers,

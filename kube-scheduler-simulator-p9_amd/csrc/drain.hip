@@ -1,0 +1,256 @@
+// Drain simulation (ksg_drain / ksg_drain_plan, include/ksg.h): can a node be
+// emptied -- its bound pods re-placed one after another, each on the lowest node
+// that admits it and counted there before the next is judged.  Part of the
+// engine's translation unit (engine.hip includes it after bound_fit.hip).
+//
+//   k_drain<false>  one block of 256 threads per candidate node x.  The subjects
+//                 (the launch inputs: per candidate a range of a list of bound
+//                 indices and victim-store offsets, ascending bound index) are
+//                 taken in order.  For a subject the block walks the nodes in
+//                 ascending tiles of kSqTile: a lane computes the codes of its
+//                 kSqNpt nodes as k_bound_fit does (sq_live, sq_walk<kPmBoundFit>,
+//                 fit_filter over the register source free_r / left), the source
+//                 lowered by the overlay's entry for the node if it has one; x
+//                 itself is no destination.  The wave's lowest passing node is
+//                 read off the ballots, one LDS atomicMin per wave gives the
+//                 tile's, and after a barrier every thread reads it.  The walk
+//                 ends at the first tile with a hit: first fit costs a loose
+//                 cluster one tile per subject, not N nodes.  Thread 0 then
+//                 counts the subject on its destination in the overlay, and the
+//                 block barriers.  At the end thread 0 stores the 32-byte struct:
+//                 nothing is accumulated across blocks.
+//   k_drain<true>   the same body for one candidate with a store of {bound, dest}
+//                 per subject (ksg_drain_plan); subjects beyond the cap get -2.
+//
+// The overlay is the drain's own placements, private to the block, in LDS (not
+// in global memory: a block's vector stores are not coherent with its reads
+// through the scalar cache): the distinct destinations, and per destination the
+// pods and the requests of the R columns added so far.  A node that passes
+// against its rows alone looks its entry up by a linear search over the distinct
+// destinations (broadcast LDS reads; first fit keeps them few) and runs
+// fit_filter once more against the lowered rows.  The overlay only lowers what
+// is left, so a node that fails without it fails with it.  Not tuned: see
+// DESIGN.md "Drain simulation".
+//
+// The tile's rows are loaded when the walk enters another tile than the one the
+// registers hold, so subjects that all hit in tile 0 load it once.
+//
+// The tile's lowest hit goes through three LDS words used in rotation, a running
+// count `it` of tile steps choosing word it % 3: the waves min into it before the
+// step's barrier, every thread reads it after the barrier, and thread 0 then
+// presets word (it + 2) % 3 -- last read before this barrier, next written
+// after the following one.  One barrier per tile step.
+//
+// Forward progress: the only waits are block barriers that every thread
+// reaches.  The subject loop's bound, the tile loop's bound and the found-break
+// are block-uniform: the subject count and the tile's hit are read from LDS
+// after a barrier, the tile count is a kernel argument.  No thread waits on
+// another block.  No loop is unbounded: subjects <= KSG_DRAIN_MAX, tiles <=
+// ceil(N / kSqTile), the overlay search <= the subjects so far, the profile walk
+// as in snapshot_query.hip.  The loops hold no return.
+#include "../../include/ksg.h"
+
+namespace ksg {
+
+using Drain = struct ::ksg_drain;  // (the function of the same name hides the struct's)
+using DrainMove = struct ::ksg_drain_move;
+static_assert(KSG_DRAIN_MAX == kDrainMax, "the header's cap is the overlay's size");
+static_assert(sizeof(Drain) == 32 && offsetof(Drain, placed) == 8 && offsetof(Drain, first_unplaced) == 20 &&
+                  offsetof(Drain, reserved) == 28,
+              "the kernel stores the struct's own layout");
+static_assert(sizeof(DrainMove) == 8 && offsetof(DrainMove, dest) == 4, "");
+// one candidate's launch input: its subjects are entries [start, start + subjects) of the lists
+struct DrainCand {
+  uint32_t start, subjects;
+  int32_t pods, daemon;
+};
+constexpr size_t kDrainLds =
+    kDrainMax * (sizeof(uint32_t) + sizeof(int32_t) + KSG_MAX_RES * sizeof(int64_t)) + 8 * sizeof(uint32_t);
+static_assert(kDrainLds < 64 * 1024, "the overlay is one static LDS allocation under 64 KB");
+
+// cand: entry 0 is the launch's first candidate, local node first_node; off / bidx: the subjects' offsets
+// into the store and bound indices; cap <= kDrainMax
+template <bool PLAN>
+__global__ __launch_bounds__(256) void k_drain(DevCluster C, DevProfile F, const uint8_t* __restrict__ store,
+                                               const DrainCand* __restrict__ cand, const uint64_t* __restrict__ off,
+                                               const int32_t* __restrict__ bidx, uint32_t first_node, uint32_t cap,
+                                               uint32_t tiles, Drain* out, DrainMove* plan) {
+  __shared__ int64_t ov_req[kDrainMax][KSG_MAX_RES];  // per distinct destination: requests added
+  __shared__ uint32_t ov_dest[kDrainMax];             // the distinct destinations (local node index)
+  __shared__ int32_t ov_cnt[kDrainMax];               // pods added
+  __shared__ uint32_t ov_n;
+  __shared__ uint32_t hit[3];
+  __shared__ uint32_t s_start, s_subjects;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t x = first_node + blockIdx.x;
+  if (tid == 0) {
+    const DrainCand c = cand[blockIdx.x];
+    s_start = c.start;
+    s_subjects = c.subjects;
+    ov_n = 0;
+    hit[0] = hit[1] = hit[2] = 0xFFFFFFFFu;
+  }
+  __syncthreads();
+  const uint32_t start = s_start, subjects = s_subjects;
+  const uint32_t n_sim = subjects < cap ? subjects : cap;
+  int64_t fr[kSqNpt][KSG_MAX_RES];
+  int32_t left[kSqNpt];
+  uint32_t loaded = 0xFFFFFFFFu, it = 0;
+  int32_t placed = 0, unplaced = 0, first_unplaced = -1;  // (thread 0's)
+#pragma unroll 1
+  for (uint32_t s = 0; s < n_sim; ++s) {
+    const ProgView V = view(store + off[start + s]);
+    const ksg_prog* h = V.h;
+    BfPod pod;
+    pod.flags = h->flags;
+#pragma unroll
+    for (uint32_t r = 0; r < KSG_MAX_RES; ++r) pod.req[r] = r < C.R ? h->req[r] : 0;
+    const uint32_t nd = ov_n;  // (after the barrier that followed its last update)
+    uint32_t found = 0xFFFFFFFFu;
+#pragma unroll 1
+    for (uint32_t t = 0; t < tiles; ++t) {
+      const uint32_t base = t * kSqTile + tid;
+      if (t != loaded) {  // (block-uniform)
+        sq_rows(C, base, fr, left);
+        loaded = t;
+      }
+      uint32_t first = 0xFFFFFFFFu;
+#pragma unroll
+      for (uint32_t k = 0; k < kSqNpt; ++k) {
+        const uint32_t n = base + k * 256;
+        bool pass = false;
+        if (n != x && sq_live(C, V, n)) {
+          const uint32_t code = sq_walk<kPmBoundFit>(C, F, V, n, [&]() -> uint32_t {
+            const uint32_t alone = fit_filter(BfSrc{fr[k], left[k]}, &pod, (uint32_t)KSG_MAX_RES);
+            if (alone) return alone;
+            for (uint32_t j = 0; j < nd; ++j) {
+              if (ov_dest[j] != n) continue;
+              int64_t f[KSG_MAX_RES];
+#pragma unroll
+              for (uint32_t r = 0; r < KSG_MAX_RES; ++r) f[r] = fr[k][r] - ov_req[j][r];
+              return fit_filter(BfSrc{f, left[k] - ov_cnt[j]}, &pod, (uint32_t)KSG_MAX_RES);
+            }
+            return 0;
+          });
+          pass = code == KSG_FILTER_PASS;
+        }
+        const unsigned long long b = __ballot(pass);
+        if (b && first == 0xFFFFFFFFu)  // (wave-uniform; a lane's nodes ascend with k)
+          first = t * kSqTile + k * 256 + (tid & ~63u) + (uint32_t)__ffsll((long long)b) - 1;
+      }
+      if (first != 0xFFFFFFFFu && lane0()) atomicMin(&hit[it % 3], first);
+      __syncthreads();
+      found = hit[it % 3];
+      if (tid == 0) hit[(it + 2) % 3] = 0xFFFFFFFFu;
+      ++it;
+      if (found != 0xFFFFFFFFu) break;  // (block-uniform)
+    }
+    if (tid == 0) {
+      const int32_t b = bidx[start + s];
+      if (found == 0xFFFFFFFFu) {
+        if (!unplaced++) first_unplaced = b;
+      } else {
+        ++placed;
+        uint32_t j = 0;
+        while (j < nd && ov_dest[j] != found) ++j;
+        if (j == nd) {  // (nd <= s < kDrainMax)
+          ov_dest[j] = found;
+          ov_cnt[j] = 0;
+#pragma unroll
+          for (uint32_t r = 0; r < KSG_MAX_RES; ++r) ov_req[j][r] = 0;
+          ov_n = nd + 1;
+        }
+        ov_cnt[j] += 1;
+#pragma unroll
+        for (uint32_t r = 0; r < KSG_MAX_RES; ++r) ov_req[j][r] += pod.req[r];
+      }
+      if (PLAN) plan[s] = DrainMove{b, found == 0xFFFFFFFFu ? -1 : (int32_t)(C.goff + found)};
+    }
+    __syncthreads();
+  }
+  if (PLAN) {
+    for (uint32_t s = n_sim + tid; s < subjects; s += 256) plan[s] = DrainMove{bidx[start + s], -2};
+  } else if (tid == 0) {
+    const DrainCand c = cand[blockIdx.x];
+    Drain d;
+    d.pods = c.pods;
+    d.daemon = c.daemon;
+    d.placed = placed;
+    d.unplaced = unplaced;
+    d.skipped = (int32_t)(subjects - n_sim);
+    d.first_unplaced = first_unplaced;
+    d.dest_nodes = (int32_t)ov_n;
+    d.reserved = 0;
+    out[blockIdx.x] = d;
+  }
+}
+
+namespace {
+// The candidates of `in` against the snapshot as the stream holds it: the launch
+// inputs through the device buffer, the structs (or the one candidate's moves)
+// back through the pinned block, one synchronisation.
+int drain_run(Engine& eng, const DrainIn& in, Drain* out, DrainMove* plan, std::string& err) {
+  Engine::Impl& I = *eng.impl();
+  const uint32_t N = I.N;
+  if (!I.F.n || I.F.pos_fit < 0) {  // (host.cpp checked the profile; the kernel reads a Fit profile)
+    err = "drain: NodeResourcesFit is not in the profile";
+    return KSG_E_INVALID;
+  }
+  const uint32_t total = in.start[in.count];
+  if ((size_t)in.first_node + in.count > N || (plan && in.count != 1)) {
+    err = "drain: candidates outside the snapshot";
+    return KSG_E_RANGE;
+  }
+  const size_t back_bytes = plan ? (size_t)total * sizeof(DrainMove) : (size_t)in.count * sizeof(Drain);
+  if (!back_bytes) return KSG_OK;
+  // the launch inputs: the subjects' store offsets, the candidates, the subjects' bound indices
+  const size_t off_bytes = (size_t)total * sizeof(uint64_t), cand_bytes = (size_t)in.count * sizeof(DrainCand);
+  const size_t in_bytes = off_bytes + cand_bytes + (size_t)total * sizeof(int32_t);
+  std::vector<uint8_t> host(in_bytes);
+  {
+    uint64_t* o64 = reinterpret_cast<uint64_t*>(host.data());
+    DrainCand* hc = reinterpret_cast<DrainCand*>(host.data() + off_bytes);
+    for (uint32_t i = 0; i < total; ++i) {
+      const int32_t b = in.subj[i];
+      if (b < 0 || (size_t)b >= I.vstore_off.size()) {  // (host.cpp ensured the store for this very bound list)
+        err = "drain: bound pod outside the victim store";
+        return KSG_E_STATE;
+      }
+      o64[i] = I.vstore_off[(size_t)b];
+    }
+    for (uint32_t c = 0; c < in.count; ++c)
+      hc[c] = DrainCand{in.start[c], in.start[c + 1] - in.start[c], in.pods[c], in.daemon[c]};
+    if (total) std::memcpy(host.data() + off_bytes + cand_bytes, in.subj, (size_t)total * sizeof(int32_t));
+  }
+  if (!I.bf_in.alloc(in_bytes, err) || !I.hr_dev.alloc(back_bytes, err)) return KSG_E_DEVICE;
+  const uint64_t* d_off = reinterpret_cast<const uint64_t*>(I.bf_in.p);
+  const DrainCand* d_cand = reinterpret_cast<const DrainCand*>(I.bf_in.p + off_bytes);
+  const int32_t* d_bidx = reinterpret_cast<const int32_t*>(I.bf_in.p + off_bytes + cand_bytes);
+  const uint32_t cap = std::min(I.drain_max, kDrainMax), tiles = (N + kSqTile - 1) / kSqTile;
+  auto enqueue = [&](hipStream_t s) -> bool {
+    HIPCHK(hipMemcpyAsync(I.bf_in.p, host.data(), in_bytes, hipMemcpyHostToDevice, s));
+    if (plan)
+      hipLaunchKernelGGL(k_drain<true>, dim3(1), dim3(256), 0, s, I.cluster(), I.F, I.vstore.p, d_cand, d_off, d_bidx,
+                         in.first_node, cap, tiles, (Drain*)nullptr, reinterpret_cast<DrainMove*>(I.hr_dev.p));
+    else
+      hipLaunchKernelGGL(k_drain<false>, dim3(in.count), dim3(256), 0, s, I.cluster(), I.F, I.vstore.p, d_cand, d_off,
+                         d_bidx, in.first_node, cap, tiles, reinterpret_cast<Drain*>(I.hr_dev.p), (DrainMove*)nullptr);
+    return true;
+  };
+  if (!sq_fetch(I, I.hr_dev.p, back_bytes, enqueue, err)) return KSG_E_DEVICE;
+  std::memcpy(plan ? (void*)plan : (void*)out, I.sq_host.p, back_bytes);
+  return KSG_OK;
+}
+}  // namespace
+
+}  // namespace ksg
+
+extern "C" int ksg_drain(ksg_ctx* ctx, uint32_t first_node, uint32_t count, struct ksg_drain* out) {
+  return ksg::drain_call(ctx, first_node, count, out != nullptr, "drain", &ksg::drain_run, out, nullptr, 0, nullptr);
+}
+
+extern "C" int ksg_drain_plan(ksg_ctx* ctx, uint32_t node, struct ksg_drain_move* out, uint32_t cap, uint32_t* n_out) {
+  if (n_out) *n_out = 0;
+  return ksg::drain_call(ctx, node, 1, out != nullptr && n_out != nullptr, "drain_plan", &ksg::drain_run, nullptr, out, cap,
+                         n_out);
+}

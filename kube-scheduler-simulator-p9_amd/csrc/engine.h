@@ -13,6 +13,8 @@
 struct ksg_filter_bucket;  // include/ksg.h
 struct ksg_bound_fit;
 struct ksg_node_evict;
+struct ksg_drain;
+struct ksg_drain_move;
 struct ksg_ctx;
 
 namespace ksg {
@@ -368,6 +370,22 @@ struct BoundFitOut {
 using BoundFitFn = int (*)(Engine& eng, uint32_t first, uint32_t count, const int32_t* own, const BoundFitOut& out,
                            std::string& err);
 
+// What the drain simulation's entry points (drain.hip) get from host.cpp's
+// drain_call: the candidates, local nodes [first_node, first_node + count), and
+// per candidate c its subjects subj[start[c] .. start[c + 1]) -- bound indices in
+// ascending order, the pods a drain leaves in place taken out -- with the bound
+// pods on the node and how many of them stay.  Exactly one of out (a struct per
+// candidate) and plan (count == 1: a move per subject) is set.
+struct DrainIn {
+  uint32_t first_node, count;
+  const uint32_t* start;  // [count + 1]
+  const int32_t* subj;    // [start[count]]
+  const int32_t* pods;    // [count]
+  const int32_t* daemon;  // [count]
+};
+using DrainFn = int (*)(Engine& eng, const DrainIn& in, struct ::ksg_drain* out, struct ::ksg_drain_move* plan,
+                        std::string& err);
+
 // The context's side of the snapshot queries (host.cpp).  Their entry points live
 // in the engine's translation unit and hand the engine function over as a
 // pointer, so that host.cpp, which also links against a stand-in for the engine
@@ -388,5 +406,8 @@ int headroom_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, co
 // ksg_bound_fit / ksg_bound_fit_nodes / ksg_node_evictability (whole: the range is every bound pod)
 int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, bool args_ok, const uint32_t* n_nodes,
                    const char* what, BoundFitFn fn, const BoundFitOut& bo);
+// ksg_drain (out) / ksg_drain_plan (plan, cap, n_out: first is the node, count 1)
+int drain_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const char* what, DrainFn fn,
+               struct ::ksg_drain* out, struct ::ksg_drain_move* plan, uint32_t cap, uint32_t* n_out);
 
 }  // namespace ksg

@@ -5389,6 +5389,7 @@ constexpr size_t kVerdictAbortWord = 8;
 static_assert((kVerdictAbortWord + 1) * sizeof(uint32_t) <= kVerdictBytes, "the abort word lies inside the verdict block");
 constexpr uint32_t kDiagMax = 1024;   // unschedulable diagnosis: slots of the device count table (KSG_DIAG_MAX)
 constexpr uint32_t kRankTile = 2048;  // ranked candidates: most nodes (keys) one block of 256 threads selects from
+constexpr uint32_t kDrainMax = 512;   // drain simulation: subjects simulated per candidate (KSG_DRAIN_MAX)
 struct Engine::Impl {
   EngineConfig cfg;
   // node-shard exchange (sharded batch path)
@@ -5580,6 +5581,10 @@ struct Engine::Impl {
   // eviction fit (bound_fit.hip): a launch's inputs, the bound pods' store offsets and own nodes
   // (its results use headroom's device block: the context lock serialises the calls)
   DBuf<uint8_t> bf_in;
+  // drain simulation (drain.hip): subjects simulated per candidate at most (KSG_DRAIN_MAX: a power of
+  // two in [2, kDrainMax]; tests reach the cap with a handful of pods); its launch inputs use bf_in and
+  // its results hr_dev
+  uint32_t drain_max = kDrainMax;
   PinnedBlock sq_host;  // the pinned block every snapshot query's answer crosses in
   DBuf<int32_t> knorm;   // normalized scores of one kept pod
   DBuf<uint8_t> vblk;     // device cycle view block (Engine::view)
@@ -5757,6 +5762,10 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
   if (env_long("KSG_DIAG_SLOTS", &v)) {  // the largest power of two <= the value, within [4, kDiagMax]
     I.diag_slots = 4;
     while (I.diag_slots < kDiagMax && 2ul * I.diag_slots <= (unsigned long)v) I.diag_slots *= 2;
+  }
+  if (env_long("KSG_DRAIN_MAX", &v)) {  // the largest power of two <= the value, within [2, kDrainMax]
+    I.drain_max = 2;
+    while (I.drain_max < kDrainMax && 2ul * I.drain_max <= (unsigned long)v) I.drain_max *= 2;
   }
   if (env_long("KSG_RUN", &v)) I.run_on = (int)v;
   if (env_long("KSG_RUN_MIN", &v)) I.run_min = std::max<uint32_t>(1, (uint32_t)v);
@@ -8587,3 +8596,4 @@ extern "C" int ksg_debug_arith(int op, const int64_t* in, uint32_t cols, int64_t
 #include "diagnosis.hip"
 #include "headroom.hip"
 #include "bound_fit.hip"
+#include "drain.hip"

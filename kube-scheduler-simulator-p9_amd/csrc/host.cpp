@@ -332,6 +332,7 @@ struct Pod {
   bool gated = false;               // spec.schedulingGates non-empty (SchedulingGates PreEnqueue)
   bool preempt_never = false;       // spec.preemptionPolicy Never (PodEligibleToPreemptOthers)
   i64 start_time = INT64_MAX;       // status.startTime, epoch seconds; none: started last (GetPodStartTime: now)
+  bool stays = false;               // owned by a DaemonSet controller, or a mirror pod: a drain leaves it (ksg_drain)
 };
 
 // RFC 3339 date-time -> seconds since the epoch (the date and time fields; a
@@ -414,6 +415,12 @@ static Pod parse_pod(const J& v) {
   if (p.ns.empty()) p.ns = "default";
   p.labels = smap(md ? (*md)["labels"] : nullptr);
   p.terminating = md && (*md)["deletionTimestamp"] && !(*md)["deletionTimestamp"]->null();
+  if (md) {  // kubectl drain --ignore-daemonsets / the autoscaler's drain: these pods are not moved
+    if (const J* ors = (*md)["ownerReferences"]; ors && ors->t == J::ARR)
+      for (auto& o : ors->items)
+        if (const J* ctl = o["controller"]; ctl && ctl->b && str_of(o["kind"]) == "DaemonSet") p.stays = true;
+    if (const J* ann = (*md)["annotations"]; ann && (*ann)["kubernetes.io/config.mirror"]) p.stays = true;
+  }
   p.req = pod_requests(sp, false);
   p.req_nz = pod_requests(sp, true);
   if (!sp) return p;
@@ -5790,6 +5797,42 @@ int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, boo
   if (bo.codes)
     for (uint32_t i = 0; i < c.hi - c.lo; ++i) bo.codes[i] = c.profile_code(bo.codes[i]);
   return KSG_OK;
+}
+
+// The drain simulation: the eviction fit's refusals and its store (every bound
+// pod's program).  The candidates' subjects come from the bound pods grouped by
+// node (bound_by_node: one counting sort per snapshot generation, ascending
+// bound index within a node) with the pods a drain leaves in place taken out.
+// The plan of one node is sized here, before the device is asked anything.
+int drain_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const char* what, DrainFn fn,
+               struct ::ksg_drain* out, struct ::ksg_drain_move* plan, uint32_t cap, uint32_t* n_out) {
+  std::unique_lock<std::recursive_mutex> lk;
+  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, (uint64_t)first + count,
+                                   [](const Cluster& c) { return (size_t)(c.hi - c.lo); }))
+    return rc;
+  auto& c = ctx->c;
+  if (!count) return KSG_OK;
+  const std::vector<uint32_t>& boff = c.bound_by_node();
+  std::vector<uint32_t> start(count + 1, 0);
+  std::vector<int32_t> subj, pods(count), daemon(count, 0);
+  for (uint32_t i = 0; i < count; ++i) {
+    const uint32_t x = first + i;
+    pods[i] = (int32_t)(boff[x + 1] - boff[x]);
+    for (uint32_t e = boff[x]; e < boff[x + 1]; ++e) {
+      const int32_t b = c.bcsr_idx[e];
+      if (c.bound[b].stays) ++daemon[i];
+      else subj.push_back(b);
+    }
+    start[i + 1] = (uint32_t)subj.size();
+  }
+  if (plan) {
+    *n_out = start[1];
+    if (cap < start[1]) return KSG_E_NOBUF;
+  }
+  if (!c.compile_queue()) return ctx->fail(c.err, KSG_E_INVALID);
+  if (!c.ensure_victim_store()) return ctx->fail(c.err, KSG_E_DEVICE);
+  const DrainIn in{first, count, start.data(), subj.data(), pods.data(), daemon.data()};
+  return ctx->done(fn(*c.eng, in, out, plan, c.err));
 }
 }  // namespace ksg
 

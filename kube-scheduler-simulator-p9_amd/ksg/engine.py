@@ -65,6 +65,27 @@ class _NodeEvict(ctypes.Structure):
 BoundFit = namedtuple("BoundFit", "node own_code other_nodes first_other")
 NodeEvict = namedtuple("NodeEvict", "pods stuck drifted")
 
+DRAIN_MAX = 512  # KSG_DRAIN_MAX
+
+
+class _Drain(ctypes.Structure):
+    _fields_ = [("pods", ctypes.c_int32), ("daemon", ctypes.c_int32), ("placed", ctypes.c_int32),
+                ("unplaced", ctypes.c_int32), ("skipped", ctypes.c_int32), ("first_unplaced", ctypes.c_int32),
+                ("dest_nodes", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class _DrainMove(ctypes.Structure):
+    _fields_ = [("bound", ctypes.c_int32), ("dest", ctypes.c_int32)]
+
+
+class Drain(namedtuple("Drain", "pods daemon placed unplaced skipped first_unplaced dest_nodes")):
+    __slots__ = ()
+
+    @property
+    def drainable(self):
+        """Every subject was simulated and found a destination."""
+        return self.unplaced == 0 and self.skipped == 0
+
 
 class _Opts(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("stream", ctypes.c_void_p), ("shard_rank", ctypes.c_uint32),
@@ -670,6 +691,35 @@ class Scheduler:
         arr = (_NodeEvict * max(n, 1))()
         self._chk(self.L.ksg_node_evictability(self.h, arr, n), "ksg_node_evictability")
         return [NodeEvict(a.pods, a.stuck, a.drifted) for a in arr[:n]]
+
+    # ---- drain simulation (ksg.h): a node's pods re-placed one after another, first fit in node order
+    def drain(self, first=0, count=None):
+        """ksg_drain: for local nodes [first, first+count) the simulated drain: [Drain(pods, daemon,
+        placed, unplaced, skipped, first_unplaced, dest_nodes)], .drainable when every subject found
+        a node.  Each subject goes to the lowest node that admits it and is counted there before
+        the next is judged: first fit, not the scheduler's own choice.  One launch for the range."""
+        self.L.ksg_drain.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_Drain)]
+        count = self.n_nodes - first if count is None else count
+        arr = (_Drain * max(count, 1))()
+        self._chk(self.L.ksg_drain(self.h, first, count, arr), "ksg_drain")
+        return [Drain(a.pods, a.daemon, a.placed, a.unplaced, a.skipped, a.first_unplaced, a.dest_nodes)
+                for a in arr[:count]]
+
+    def drain_plan(self, node):
+        """ksg_drain_plan: the subjects of local node `node` in simulation order, [(bound index,
+        destination)]: a global node index, -1 unplaced, -2 beyond KSG_DRAIN_MAX (not simulated)."""
+        self.L.ksg_drain_plan.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(_DrainMove), ctypes.c_uint32,
+                                          ctypes.POINTER(ctypes.c_uint32)]
+        n = ctypes.c_uint32()
+        cap = 128  # (most nodes hold fewer pods: one call; KSG_E_NOBUF leaves the count in n)
+        while True:
+            arr = (_DrainMove * cap)()
+            rc = self.L.ksg_drain_plan(self.h, node, arr, cap, ctypes.byref(n))
+            if rc != -5:
+                break
+            cap = n.value
+        self._chk(rc, "ksg_drain_plan")
+        return [(a.bound, a.dest) for a in arr[:n.value]]
 
     def node_nonzero(self):
         """NonZeroRequested (cpu milli, memory bytes) rows of every local node."""
