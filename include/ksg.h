@@ -54,7 +54,8 @@ extern "C" {
  * ksg_headroom_nodes, ksg_resource_name, KSG_HEADROOM_BOUNDS; ksg_bound_count,
  * ksg_bound_pod, ksg_bound_fit (the call and the struct), ksg_bound_fit_nodes,
  * ksg_node_evictability, ksg_node_evict; ksg_drain (the call and the struct),
- * ksg_drain_plan, ksg_drain_move, KSG_DRAIN_MAX. */
+ * ksg_drain_plan, ksg_drain_move, KSG_DRAIN_MAX; ksg_scale_up (the call and the
+ * struct), ksg_scale_up_plan, KSG_SCALE_MAX. */
 #define KSG_ABI_VERSION 4
 
 #define KSG_OK 0
@@ -530,6 +531,77 @@ struct ksg_drain {            /* 32 bytes, per candidate node */
 struct ksg_drain_move { int32_t bound; int32_t dest; };  /* dest: global node, -1 unplaced, -2 skipped */
 int ksg_drain(ksg_ctx* ctx, uint32_t first_node, uint32_t count, struct ksg_drain* out);
 int ksg_drain_plan(ksg_ctx* ctx, uint32_t node, struct ksg_drain_move* out, uint32_t cap, uint32_t* n_out);
+
+/* Scale-up simulation (the cluster-autoscaler's scale-up estimate, its binpacking
+ * estimator; Karpenter's provisioning loop): for pods that do not fit, which node
+ * group to grow, by how many nodes, and which pods still stay pending.  Per
+ * template the listed pods are packed onto fresh nodes of the template's shape,
+ * first fit in bin order, the same rule as the drain above.  One block per
+ * template on the device (csrc/scale_up.hip), every template of a call in one
+ * launch; the static verdicts of all (pod, template) pairs in one launch before.
+ * Pods.  pods[] lists queue indices in packing order.  The order is the caller's
+ * choice (the autoscaler sorts by decreasing size); the call does not sort.  An
+ * index listed twice is packed twice, as two replicas.  A pod's own scheduling
+ * state (pending, scheduled, unschedulable) does not matter to the call.
+ * Templates.  templates[] lists local node indices.  A fresh node of template t
+ * has t's allocatable columns, allowed pod count, labels, taints and
+ * spec.unschedulable flag, exactly as the device snapshot holds them when the
+ * call runs (every event applied so far; the call is ordered on the context
+ * stream after any pending delta).
+ * Base load.  A fresh node starts with the requests and the count of t's bound
+ * pods that a drain leaves in place: pods owned by a DaemonSet controller and
+ * mirror pods (ksg_drain above), as the autoscaler's template keeps them.  They
+ * are counted in base_pods.  t's other bound pods do not count, queue pods placed
+ * on t do not count, requested(t) does not count.
+ * open(p, t).  Pod p is open for template t when all of these hold, and closed
+ * for t otherwise: p's PreFilter neither rejected it nor ended in an error; p has
+ * no PreFilterResult node set (such a set names existing nodes); with NodeName in
+ * the profile p sets no spec.nodeName (a fresh node carries a new name); the
+ * profile's TaintToleration, NodeAffinity and NodeUnschedulable Filters pass on
+ * node t.  Limitation: the labels are t's verbatim, kubernetes.io/hostname
+ * included, so a selector on the template's own host name matches the fresh
+ * nodes too; the autoscaler's templates have the same limitation.
+ * Packing.  For each pod in list order: a closed pod is counted in `closed` and
+ * the simulation goes on.  Otherwise the pod goes to the lowest opened bin whose
+ * remaining room admits it, the test being NodeResourcesFit's against
+ * allocatable_r(t) - base_r - the sum of the requests packed into the bin, and
+ * allowed(t) - base_pods - the pods packed into the bin (a zero-request pod is
+ * bounded by the pod room alone).  If no opened bin admits it, an empty fresh
+ * node is tested: if that does not admit it, it is counted in `too_big`;
+ * otherwise, if nodes == max_nodes, in `over_cap`; otherwise bin `nodes` is
+ * opened and the pod placed there.  The simulation always goes on with the next
+ * pod.  Arithmetic is integer and exact.  Templates are independent of each
+ * other; no scheduling state changes, and two calls return the same bytes.
+ * First fit in bin order is what a scale-up estimate does; it is not the
+ * scheduler's choice among the opened nodes, and the answer is an estimate of
+ * the nodes needed, not a placement the scheduler will make.
+ * max_nodes lies in [1, KSG_SCALE_MAX].  (Environment KSG_SCALE_MAX, read at
+ * ksg_create: a power of two in [2, 1024] that lowers the upper bound; tests reach
+ * it with a handful of pods.)
+ * ksg_scale_up fills out[i] for templates[i].  ksg_scale_up_plan returns for one
+ * template the bin of every listed pod: bin_out[i] >= 0 the bin, -1 closed, -2 too
+ * big, -3 over the cap.
+ * Profiles, refusals and errors are those of ksg_drain: a sharded context or a
+ * profile outside headroom's closed form: KSG_E_INVALID; out, bin_out, pods or
+ * templates NULL with a non-zero count, a queue index outside the queue, a
+ * template outside the local nodes, max_nodes outside its range: KSG_E_RANGE;
+ * n_templates == 0: KSG_OK, nothing written; n_pods == 0: structs with every count
+ * 0, first_unpacked -1 and base_pods set (the plan writes nothing). */
+#define KSG_SCALE_MAX 1024
+struct ksg_scale_up {          /* 32 bytes, per template */
+  int32_t nodes;           /* fresh nodes opened */
+  int32_t packed;          /* pods of the list placed on one of them */
+  int32_t closed;          /* pods a node of this shape never admits (see above) */
+  int32_t too_big;         /* open pods that an empty fresh node does not admit */
+  int32_t over_cap;        /* open pods that fit an empty node, met when `nodes` == max_nodes and no opened node had room */
+  int32_t first_unpacked;  /* position in the pod list of the first pod not packed, -1 when none */
+  int32_t base_pods;       /* pods every fresh node starts with (the template's DaemonSet / mirror pods) */
+  int32_t reserved;        /* 0 */
+};                          /* satisfied: packed == n_pods */
+int ksg_scale_up(ksg_ctx* ctx, const uint32_t* pods, uint32_t n_pods, const uint32_t* templates,
+                 uint32_t n_templates, uint32_t max_nodes, struct ksg_scale_up* out);
+int ksg_scale_up_plan(ksg_ctx* ctx, const uint32_t* pods, uint32_t n_pods, uint32_t template_node,
+                      uint32_t max_nodes, int32_t* bin_out /* n_pods entries */);
 
 /* PostFilter (wrappedplugin.go:550-577 -> store.go:442 AddPostFilterResult):
  * DefaultPreemption's dry run for an unschedulable pod q (PodEligibleToPreemptOthers,

@@ -15,6 +15,7 @@ struct ksg_bound_fit;
 struct ksg_node_evict;
 struct ksg_drain;
 struct ksg_drain_move;
+struct ksg_scale_up;
 struct ksg_ctx;
 
 namespace ksg {
@@ -386,6 +387,23 @@ struct DrainIn {
 using DrainFn = int (*)(Engine& eng, const DrainIn& in, struct ::ksg_drain* out, struct ::ksg_drain_move* plan,
                         std::string& err);
 
+// What the scale-up simulation's entry points (scale_up.hip) get from host.cpp's
+// scale_up_call: the pod list (queue indices, checked), the templates (local
+// nodes, checked) and per template the base load a fresh node starts with -- the
+// requests on the cluster's resource columns and the count of the template's
+// bound pods that a drain leaves in place.  Exactly one of out (a struct per
+// template) and plan (n_templates == 1: a bin per listed pod) is set.
+struct ScaleUpIn {
+  const uint32_t* pods;
+  uint32_t n_pods;
+  const uint32_t* templates;
+  uint32_t n_templates;
+  uint32_t max_nodes;
+  const int64_t* base_req;   // [n_templates][KSG_MAX_RES]
+  const int32_t* base_pods;  // [n_templates]
+};
+using ScaleUpFn = int (*)(Engine& eng, const ScaleUpIn& in, struct ::ksg_scale_up* out, int32_t* plan, std::string& err);
+
 // The context's side of the snapshot queries (host.cpp).  Their entry points live
 // in the engine's translation unit and hand the engine function over as a
 // pointer, so that host.cpp, which also links against a stand-in for the engine
@@ -409,5 +427,9 @@ int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, boo
 // ksg_drain (out) / ksg_drain_plan (plan, cap, n_out: first is the node, count 1)
 int drain_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const char* what, DrainFn fn,
                struct ::ksg_drain* out, struct ::ksg_drain_move* plan, uint32_t cap, uint32_t* n_out);
+// ksg_scale_up (out) / ksg_scale_up_plan (plan: one template)
+int scale_up_call(ksg_ctx* ctx, const uint32_t* pods, uint32_t n_pods, const uint32_t* templates, uint32_t n_templates,
+                  uint32_t max_nodes, bool args_ok, const char* what, ScaleUpFn fn, struct ::ksg_scale_up* out,
+                  int32_t* plan);
 
 }  // namespace ksg

@@ -5390,6 +5390,7 @@ static_assert((kVerdictAbortWord + 1) * sizeof(uint32_t) <= kVerdictBytes, "the 
 constexpr uint32_t kDiagMax = 1024;   // unschedulable diagnosis: slots of the device count table (KSG_DIAG_MAX)
 constexpr uint32_t kRankTile = 2048;  // ranked candidates: most nodes (keys) one block of 256 threads selects from
 constexpr uint32_t kDrainMax = 512;   // drain simulation: subjects simulated per candidate (KSG_DRAIN_MAX)
+constexpr uint32_t kScaleMax = 1024;  // scale-up simulation: fresh nodes one template opens at most (KSG_SCALE_MAX)
 struct Engine::Impl {
   EngineConfig cfg;
   // node-shard exchange (sharded batch path)
@@ -5585,6 +5586,9 @@ struct Engine::Impl {
   // two in [2, kDrainMax]; tests reach the cap with a handful of pods); its launch inputs use bf_in and
   // its results hr_dev
   uint32_t drain_max = kDrainMax;
+  // scale-up simulation (scale_up.hip): the upper bound of max_nodes (KSG_SCALE_MAX: a power of two in
+  // [2, kScaleMax]); its launch inputs and the open bytes use bf_in and its results hr_dev
+  uint32_t scale_max = kScaleMax;
   PinnedBlock sq_host;  // the pinned block every snapshot query's answer crosses in
   DBuf<int32_t> knorm;   // normalized scores of one kept pod
   DBuf<uint8_t> vblk;     // device cycle view block (Engine::view)
@@ -5766,6 +5770,10 @@ bool Engine::init(const EngineConfig& cfg, std::string& err) {
   if (env_long("KSG_DRAIN_MAX", &v)) {  // the largest power of two <= the value, within [2, kDrainMax]
     I.drain_max = 2;
     while (I.drain_max < kDrainMax && 2ul * I.drain_max <= (unsigned long)v) I.drain_max *= 2;
+  }
+  if (env_long("KSG_SCALE_MAX", &v)) {  // the same scheme, within [2, kScaleMax]
+    I.scale_max = 2;
+    while (I.scale_max < kScaleMax && 2ul * I.scale_max <= (unsigned long)v) I.scale_max *= 2;
   }
   if (env_long("KSG_RUN", &v)) I.run_on = (int)v;
   if (env_long("KSG_RUN_MIN", &v)) I.run_min = std::max<uint32_t>(1, (uint32_t)v);
@@ -8597,3 +8605,4 @@ extern "C" int ksg_debug_arith(int op, const int64_t* in, uint32_t cols, int64_t
 #include "headroom.hip"
 #include "bound_fit.hip"
 #include "drain.hip"
+#include "scale_up.hip"

@@ -5834,6 +5834,52 @@ int drain_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const
   const DrainIn in{first, count, start.data(), subj.data(), pods.data(), daemon.data()};
   return ctx->done(fn(*c.eng, in, out, plan, c.err));
 }
+
+// The scale-up simulation: the drain's refusals; the lists are checked under the
+// lock the gate took (the gate sees the empty range).  The listed queue pods'
+// programs are compiled and refreshed as headroom's; the base load of a template
+// is summed here from the bound pods grouped by node (bound_by_node, Pod::stays),
+// so the device reads no bound pod and the victim store is not needed.  fn checks
+// max_nodes against the engine's cap before anything else and answers an empty
+// template list with KSG_OK.
+int scale_up_call(ksg_ctx* ctx, const uint32_t* pods, uint32_t n_pods, const uint32_t* templates, uint32_t n_templates,
+                  uint32_t max_nodes, bool args_ok, const char* what, ScaleUpFn fn, struct ::ksg_scale_up* out,
+                  int32_t* plan) {
+  std::unique_lock<std::recursive_mutex> lk;
+  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, 0, [](const Cluster&) { return (size_t)0; }))
+    return rc;
+  auto& c = ctx->c;
+  for (uint32_t i = 0; i < n_pods; ++i)
+    if (pods[i] >= c.queue.size()) return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
+  for (uint32_t i = 0; i < n_templates; ++i)
+    if (templates[i] >= c.hi - c.lo) return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
+  std::vector<int64_t> base_req((size_t)n_templates * KSG_MAX_RES, 0);
+  std::vector<int32_t> base_pods(n_templates, 0);
+  if (n_templates) {
+    if (!c.compile_queue()) return ctx->fail(c.err, KSG_E_INVALID);
+    std::vector<uint32_t> listed(pods, pods + n_pods);
+    std::sort(listed.begin(), listed.end());
+    listed.erase(std::unique(listed.begin(), listed.end()), listed.end());
+    for (const uint32_t q : listed)
+      if (!c.refresh_programs(q, 1)) return ctx->fail(c.err, KSG_E_DEVICE);
+    const std::vector<uint32_t>& boff = c.bound_by_node();
+    std::vector<host::i64> rq;
+    for (uint32_t i = 0; i < n_templates; ++i) {
+      const uint32_t t = templates[i];
+      for (uint32_t e = boff[t]; e < boff[t + 1]; ++e) {
+        const host::Pod& p = c.bound[c.bcsr_idx[e]];
+        if (!p.stays) continue;
+        host::i64 nzc, nzm;
+        c.add_requests(p, rq, nzc, nzm);
+        for (size_t r = 0; r < rq.size() && r < KSG_MAX_RES; ++r)
+          base_req[(size_t)i * KSG_MAX_RES + r] = host::wadd(base_req[(size_t)i * KSG_MAX_RES + r], rq[r]);
+        ++base_pods[i];
+      }
+    }
+  }
+  const ScaleUpIn in{pods, n_pods, templates, n_templates, max_nodes, base_req.data(), base_pods.data()};
+  return ctx->done(fn(*c.eng, in, out, plan, c.err));
+}
 }  // namespace ksg
 
 // the bound pods, the subjects of the eviction fit (include/ksg.h); host state only

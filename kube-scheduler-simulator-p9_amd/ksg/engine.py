@@ -87,6 +87,24 @@ class Drain(namedtuple("Drain", "pods daemon placed unplaced skipped first_unpla
         return self.unplaced == 0 and self.skipped == 0
 
 
+SCALE_MAX = 1024  # KSG_SCALE_MAX
+
+
+class _ScaleUp(ctypes.Structure):
+    _fields_ = [("nodes", ctypes.c_int32), ("packed", ctypes.c_int32), ("closed", ctypes.c_int32),
+                ("too_big", ctypes.c_int32), ("over_cap", ctypes.c_int32), ("first_unpacked", ctypes.c_int32),
+                ("base_pods", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class ScaleUp(namedtuple("ScaleUp", "nodes packed closed too_big over_cap first_unpacked base_pods")):
+    __slots__ = ()
+
+    @property
+    def satisfied(self):
+        """Every pod of the list was packed."""
+        return self.closed == 0 and self.too_big == 0 and self.over_cap == 0
+
+
 class _Opts(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("stream", ctypes.c_void_p), ("shard_rank", ctypes.c_uint32),
                 ("shard_count", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
@@ -720,6 +738,34 @@ class Scheduler:
             cap = n.value
         self._chk(rc, "ksg_drain_plan")
         return [(a.bound, a.dest) for a in arr[:n.value]]
+
+    # ---- scale-up simulation (ksg.h): a pod list packed onto fresh nodes of a template, first fit in bin order
+    _U32P = ctypes.POINTER(ctypes.c_uint32)
+
+    def scale_up(self, pods, templates, max_nodes=SCALE_MAX):
+        """ksg_scale_up: the queue indices `pods`, in this order, packed onto fresh nodes shaped like each
+        local node of `templates`: [ScaleUp(nodes, packed, closed, too_big, over_cap, first_unpacked,
+        base_pods)], .satisfied when every pod was packed.  One launch for all templates."""
+        self.L.ksg_scale_up.argtypes = [ctypes.c_void_p, self._U32P, ctypes.c_uint32, self._U32P, ctypes.c_uint32,
+                                        ctypes.c_uint32, ctypes.POINTER(_ScaleUp)]
+        pods, templates = list(pods), list(templates)
+        p = (ctypes.c_uint32 * max(len(pods), 1))(*pods)
+        t = (ctypes.c_uint32 * max(len(templates), 1))(*templates)
+        arr = (_ScaleUp * max(len(templates), 1))()
+        self._chk(self.L.ksg_scale_up(self.h, p, len(pods), t, len(templates), max_nodes, arr), "ksg_scale_up")
+        return [ScaleUp(a.nodes, a.packed, a.closed, a.too_big, a.over_cap, a.first_unpacked, a.base_pods)
+                for a in arr[:len(templates)]]
+
+    def scale_up_plan(self, pods, template, max_nodes=SCALE_MAX):
+        """ksg_scale_up_plan: for local node `template` the bin of every listed pod, in list order: >= 0 the
+        fresh node, -1 closed, -2 too big for an empty node, -3 over max_nodes."""
+        self.L.ksg_scale_up_plan.argtypes = [ctypes.c_void_p, self._U32P, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32)]
+        pods = list(pods)
+        p = (ctypes.c_uint32 * max(len(pods), 1))(*pods)
+        bins = (ctypes.c_int32 * max(len(pods), 1))()
+        self._chk(self.L.ksg_scale_up_plan(self.h, p, len(pods), template, max_nodes, bins), "ksg_scale_up_plan")
+        return list(bins[:len(pods)])
 
     def node_nonzero(self):
         """NonZeroRequested (cpu milli, memory bytes) rows of every local node."""
