@@ -4247,7 +4247,19 @@ struct Delta {
 #define KSG_HSLOTS 128  // LDS hash tables: node -> prior entry / picks (<= 32 keys each)
 struct PickTab {        // nodes picked by the window's pods under one iteration's S
   int32_t node[KSG_HSLOTS];  // -1 empty
-  int32_t first[KSG_HSLOTS], last[KSG_HSLOTS], cnt[KSG_HSLOTS];
+  int32_t first[KSG_HSLOTS];  // its first picker (the later ones: PickRow::nx)
+};
+// Row table of one S: entry a is what every pod b > a needs of pod a's pick, built
+// once per S (win_fill_rows) instead of by each of the up to 31 phase-A lanes.
+struct PickRow {
+  RowV base;      // the node's row at the window's start (its origin's start row)
+  RowV after;     // ... after the picks of all pods <= a
+  RowV snap;      // the row the eval blocks judged it on (the snapshot)
+  int32_t node;   // S[a] (-1: no pick; the rows then mean nothing)
+  int32_t nx;     // the next pod after a picking the same node (KSG_BATCH: none)
+  // the guess's pick of a candidate rank >= KSG_STAGE: its rows, which come from
+  // global memory, are not stored yet; the first iteration's phase A loads and stores them
+  int32_t deep, pad;
 };
 struct WinLDS {
   uint64_t key[KSG_BATCH][KSG_CAND];    // candidate keys (sorted, 0 = none)
@@ -4268,6 +4280,7 @@ struct WinLDS {
   int32_t ptn[KSG_HSLOTS], pte[KSG_HSLOTS];  // prior node -> entry
   int32_t gtn[KSG_HSLOTS], gtf[KSG_HSLOTS];  // guess rounds: node -> smallest proposer
   PickTab pick[3];                      // per S buffer
+  PickRow pr[KSG_BATCH];               // per-pick row table of the current S (see PickRow)
   uint64_t kc[KSG_BATCH][KSG_CAND];     // per iteration: candidate keys, 0 where the node was touched
   uint64_t rk[KSG_BATCH][KSG_BATCH];    // per iteration: key of pod b on the node pod a < b picked
   int8_t rdf[KSG_BATCH][KSG_BATCH];     // its feasible-count change vs the snapshot
@@ -4322,14 +4335,10 @@ __device__ __forceinline__ int tab_find(const int32_t* nodes, int32_t x) {
 __device__ __forceinline__ void pick_insert(PickTab& T, int32_t x, int b) {
   uint32_t h = tab_claim(T.node, x);
   atomicMin(&T.first[h], b);
-  atomicMax(&T.last[h], b);
-  atomicAdd(&T.cnt[h], 1);
 }
 __device__ __forceinline__ void pick_clear(PickTab& T, int i) {  // i < KSG_HSLOTS
   T.node[i] = -1;
   T.first[i] = KSG_BATCH;
-  T.last[i] = -1;
-  T.cnt[i] = 0;
 }
 // first pod picking node x under T (KSG_BATCH: none)
 __device__ __forceinline__ int first_pick(const PickTab& T, int32_t x) {
@@ -4378,15 +4387,49 @@ __device__ __forceinline__ void apply_delta(RowV& r, const Delta& d, uint32_t R)
   r.nzm += d.nzm;
   r.podcnt += d.pods;
 }
-// Requests of the picks of node S[a] by pods <= a, and the next pod after a picking it.
-__device__ __forceinline__ void pick_chain(const WinLDS& L, const int32_t* S, int a, int32_t x, Delta& cum, int& nx) {
-  cum = Delta{};
-  nx = KSG_BATCH;
-  for (int j = 0; j < KSG_BATCH; ++j)
-    if (S[j] == x) {
-      if (j <= a) delta_add(cum, L.pod[j]);
-      else if (nx == KSG_BATCH) nx = j;
-    }
+// The row table of the picks S (origins O), by the whole block: the 32 lanes of
+// group a = tid / 32 compare S[a] with every pod's pick (who else picks the node:
+// the requests of the picks <= a, and nx); its lanes 0..2 store after / base /
+// snap.  An entry whose node stays keeps base and snap (a deep-rank origin is
+// loaded from global memory once per pick, not per iteration), and below `keep`
+// (the stable prefix: the picks <= a are final) its row after as well.
+// (base and snap belong to the node, whichever origin names it: a node of
+// P_{W-1} is only ever named by its list entry — its candidates are masked by
+// pmask and win_exact_select maps it to the entry — and every other origin of a
+// node reads the same row as of the window's start.  So O is not compared here,
+// and a table built under one iteration's O stands for the next one's.)
+template <bool PER>
+__device__ __forceinline__ void win_fill_rows(const DevCluster& C, WinLDS& L, const WinArgs& A, const int32_t* S,
+                                              const int32_t* O, int nb, int keep, uint32_t R, int tid) {
+  const int a = tid >> 5, j = tid & 31;
+  const int32_t Sa = S[a], Sj = S[j];  // (-1 from nb on)
+  PickRow& e = L.pr[a];
+  const bool same = e.node == Sa;  // (read by the whole group, ahead of the ballot and of lane 0's store below)
+  const uint32_t m = (uint32_t)(__ballot(Sa >= 0 && Sj == Sa) >> (tid & 32));
+  if (a >= nb || j > 2) return;
+  if (j == 0) {
+    const uint32_t later = a < KSG_BATCH - 1 ? m & (~0u << (a + 1)) : 0u;
+    e.nx = later ? __ffs((int)later) - 1 : KSG_BATCH;
+    e.node = Sa;
+    e.deep = 0;  // (the first iteration stored the rows of the guess's deep picks)
+  }
+  if (Sa < 0 || (same && a < keep)) return;
+  RowV st, snap;
+  if (same) {
+    st = e.base;
+    snap = e.snap;
+  } else {
+    origin_rows<PER>(C, L, A, O[a], st, snap);
+  }
+  if (j == 0) {
+    Delta cum{};
+    for (uint32_t le = m & (~0u >> (KSG_BATCH - 1 - a)); le; le &= le - 1) delta_add(cum, L.pod[__ffs((int)le) - 1]);
+    apply_delta(st, cum, R);
+    e.after = st;
+  } else if (!same) {
+    if (j == 1) e.base = st;
+    else e.snap = snap;
+  }
 }
 __device__ __forceinline__ uint64_t max3u(uint64_t a, uint64_t b, uint64_t c) {
   uint64_t m = a > b ? a : b;
@@ -4741,10 +4784,31 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
         else pok = false;
       }
     }
-    if (valid) {
-      L.S[0][b] = node;
-      L.O[0][b] = org;
+    if (lane < KSG_BATCH) {  // no two pods of the guess pick one node: every entry of the row table is its node's only pick
+      PickRow& e = L.pr[b];
+      e.node = node;
+      e.nx = KSG_BATCH;
+      if (valid) {
+        L.S[0][b] = node;
+        L.O[0][b] = org;
+      }
+      // (a deep rank's row is a global load: wave 0 alone would wait for it here
+      // with fifteen waves at the barrier, so phase A, where every wave has loads
+      // in flight anyway, fetches it: see PickRow::deep; measured both ways,
+      // DESIGN.md "Replay core")
+      const bool deep = node >= 0 && org >= 64 && ((org - 64) & 63) >= KSG_STAGE;
+      e.deep = deep ? 1 : 0;
       if (node >= 0) pick_insert(L.pick[0], node, b);
+      if (node >= 0 && !deep) {
+        RowV st, snap;
+        origin_rows<PER>(C, L, A, org, st, snap);
+        e.base = st;
+        e.snap = snap;
+        Delta d;
+        delta_of(L.pod[b], d);
+        apply_delta(st, d, R);
+        e.after = st;
+      }
     }
   }
   lds_barrier();
@@ -4762,6 +4826,18 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
     // that an earlier pick touched.
     if (wave < 8) {
       const int p_hi = nb * (nb - 1) / 2;
+      // (the last pod's deep pick has no pair (b, a) to fetch its rows: a lane no pair ever occupies does)
+      if (iters == 0 && tid == 8 * 64 - 1 && L.pr[nb - 1].deep) {
+        PickRow& e = L.pr[nb - 1];
+        RowV st, snap;
+        origin_rows<PER>(C, L, A, L.O[cur][nb - 1], st, snap);
+        e.base = st;
+        e.snap = snap;
+        Delta d;
+        delta_of(L.pod[nb - 1], d);
+        apply_delta(st, d, R);
+        e.after = st;
+      }
 #pragma unroll 1
       for (int base = stable * (stable - 1) / 2 + wave * 64; base < p_hi; base += 8 * 64) {
         const int p = base + lane;
@@ -4769,7 +4845,8 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
           int b = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
           b = b * (b - 1) / 2 > p ? b - 1 : ((b + 1) * b / 2 <= p ? b + 1 : b);
           const int a = p - b * (b - 1) / 2;
-          const int32_t Sv = L.S[cur][a];
+          PickRow& e = L.pr[a];  // (of S[cur]: the guess's, or win_fill_rows')
+          const int32_t Sv = e.node;
           uint64_t k = 0;
           int df = 0, dT = 0, dA = 0;
           PatchV pt;
@@ -4777,16 +4854,25 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
           pt.fitba = pt.total = 0;
           pt.raw = 0;
           if (Sv >= 0) {
-            int nx = KSG_BATCH;
-            Delta cum;
-            delta_of(L.pod[a], cum);
             if (iters == 0) STAMP(24);
-            if (T.cnt[tab_find(T.node, Sv)] > 1) pick_chain(L, L.S[cur], a, Sv, cum, nx);  // picked twice (rare)
+            const int nx = e.nx;
             if (iters == 0) STAMP(25);
             if (nx >= b) {  // a is the last pick of the node before b
               RowV cur_r, snap;
-              origin_rows<PER>(C, L, A, L.O[cur][a], cur_r, snap);
-              apply_delta(cur_r, cum, R);
+              if (e.deep) {  // (first iteration, a guess's deep pick: nobody else picks its node)
+                origin_rows<PER>(C, L, A, L.O[cur][a], cur_r, snap);
+                if (b == a + 1) {
+                  e.base = cur_r;
+                  e.snap = snap;
+                }
+                Delta d;
+                delta_of(L.pod[a], d);
+                apply_delta(cur_r, d, R);
+                if (b == a + 1) e.after = cur_r;
+              } else {
+                cur_r = e.after;
+                snap = e.snap;
+              }
               const PodLite* h = &L.pod[b];
               int32_t fs, bs;
               int64_t tot;
@@ -4837,62 +4923,124 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
     if (iters == 0) STAMP(22);
     // phase B: per pod, the best of (untouched candidates, P_{W-1} nodes no
     // earlier pick touched, re-evaluated picks); waves own pods 2w and 2w+1.
+    // The two pods' chains are independent: both pods' loads first, the reductions
+    // in step, and one tail on lanes 0 (pod 2w) and 32 (pod 2w+1) at once.  (The
+    // static profiles keep one pod after the other: paired, their variant, at the
+    // 128-VGPR cap, spills.)
+    if constexpr (STAT) {
 #pragma unroll 1
-    for (int hh = 0; hh < 2; ++hh) {
-      const int b = 2 * wave + hh;
-      if (b >= nb) break;
-      if (b < stable) {
+      for (int hh = 0; hh < 2; ++hh) {
+        const int b = 2 * wave + hh;
+        if (b >= nb) break;
+        if (b < stable) {
+          if (lane == 0) {
+            int32_t s = L.S[cur][b];
+            L.S[nxt][b] = s;
+            L.O[nxt][b] = L.O[cur][b];
+            if (s >= 0) pick_insert(L.pick[nxt], s, b);
+          }
+          continue;
+        }
+        const bool pact = lane < np && L.pf[lane & 31] >= b;
+        const uint64_t kc = L.kc[b][lane];
+        const uint64_t kp = pact ? L.pkey[b][lane & 31] : 0;
+        const uint64_t kr = lane < b ? L.rk[b][lane & 31] : 0;
+        const int df = (pact ? (int)L.pdf[b][lane & 31] : 0) + (lane < b ? (int)L.rdf[b][lane & 31] : 0);
+        const uint64_t best = wave_max(max3u(kc, kp, kr));
+        // feasible and achiever counts in one reduction (per lane each change is in [-2, 2])
+        const int dT = (pact ? (int)L.pdfT[b][lane & 31] : 0) + (lane < b ? (int)L.rdfT[b][lane & 31] : 0);
+        const int dA = (pact ? (int)L.pdfA[b][lane & 31] : 0) + (lane < b ? (int)L.rdfA[b][lane & 31] : 0);
+        const int sum = wave_sum((df + 2) | ((dT + 2) << 10) | ((dA + 2) << 20));
+        const int feasible = L.feas[b] + (sum & 1023) - 128;
+        const int achT = L.achT[b] + ((sum >> 10) & 1023) - 128, achA = L.achA[b] + ((sum >> 20) & 1023) - 128;
+        const bool na_on = F.pos_na >= 0 && !(L.pod[b].flags & KPF_SKIP_NA_SCORE);
+        const bool fb = !(L.pod[b].flags & KPF_PREFILTER_ERROR) && !na_prescore_error(L.pod[b].flags, feasible) &&
+                        feasible > 0 && ((F.pos_taint >= 0 && achT <= 0) || (na_on && achA <= 0));
+        const bool perr = (L.pod[b].flags & KPF_PREFILTER_ERROR) != 0 || na_prescore_error(L.pod[b].flags, feasible);
+        const int32_t sel = (feasible > 0 && best && !perr) ? (int32_t)(best & 0xFFFFFull) : -1;
+        const unsigned long long mc = __ballot(best && kc == best), mp = __ballot(best && kp == best),
+                                 mr = __ballot(best && kr == best);
+        if (lane == 0) L.fbf[b] = fb ? 1 : 0;
+        if (fb) continue;  // win_exact_select below
         if (lane == 0) {
+          L.xmt[b] = L.mt[b] < 0 ? 0 : L.mt[b];
+          L.xma[b] = (F.pos_na < 0 || (L.pod[b].flags & KPF_SKIP_NA_SCORE) || L.ma[b] < 0) ? 0 : L.ma[b];
+          int32_t org = -1;
+          if (mc) org = 64 + b * 64 + (__ffsll((long long)mc) - 1);
+          else if (mp) org = __ffsll((long long)mp) - 1;
+          else if (mr) org = L.O[cur][__ffsll((long long)mr) - 1];
+          L.S[nxt][b] = sel;
+          L.O[nxt][b] = sel >= 0 ? org : -1;
+          if (sel >= 0) pick_insert(L.pick[nxt], sel, b);
+          SumLite& sm = L.sum[b];
+          sm.best_key = sel >= 0 ? (feasible == 1 ? (best & 0xFFFFFFFFFFull) : best) : 0;
+          sm.selected = sel;
+          sm.feasible = feasible;
+          sm.status = perr ? 2 : (sel >= 0 ? 0 : 1);
+        }
+      }
+    } else {
+      const int b0 = 2 * wave;  // (b0 + 1 <= 31: in bounds past nb, and nothing of a dead pod is stored)
+      uint64_t kc[2], kp[2], kr[2], best[2];
+      int pk[2], sum[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int b = b0 + hh;
+        const bool pact = lane < np && L.pf[lane & 31] >= b;
+        kc[hh] = L.kc[b][lane];
+        kp[hh] = pact ? L.pkey[b][lane & 31] : 0;
+        kr[hh] = lane < b ? L.rk[b][lane & 31] : 0;
+        const int df = (pact ? (int)L.pdf[b][lane & 31] : 0) + (lane < b ? (int)L.rdf[b][lane & 31] : 0);
+        pk[hh] = df;
+      }
+      {  // wave_max of both pods' keys: high words, then the low words under the winning high word
+        const uint64_t m0 = max3u(kc[0], kp[0], kr[0]), m1 = max3u(kc[1], kp[1], kr[1]);
+        const uint32_t h0 = (uint32_t)(m0 >> 32), h1 = (uint32_t)(m1 >> 32);
+        const uint32_t mh0 = __ockl_wfred_max_u32(h0), mh1 = __ockl_wfred_max_u32(h1);
+        const uint32_t ml0 = __ockl_wfred_max_u32(h0 == mh0 ? (uint32_t)m0 : 0u),
+                       ml1 = __ockl_wfred_max_u32(h1 == mh1 ? (uint32_t)m1 : 0u);
+        sum[0] = wave_sum(pk[0]);
+        sum[1] = wave_sum(pk[1]);
+        best[0] = ((uint64_t)mh0 << 32) | ml0;
+        best[1] = ((uint64_t)mh1 << 32) | ml1;
+      }
+      unsigned long long mc[2], mp[2], mr[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        mc[hh] = __ballot(best[hh] && kc[hh] == best[hh]);
+        mp[hh] = __ballot(best[hh] && kp[hh] == best[hh]);
+        mr[hh] = __ballot(best[hh] && kr[hh] == best[hh]);
+      }
+      const int hh = lane >> 5, b = b0 + hh;
+      if ((lane & 31) == 0 && b < nb) {
+        if (b < stable) {
           int32_t s = L.S[cur][b];
           L.S[nxt][b] = s;
           L.O[nxt][b] = L.O[cur][b];
           if (s >= 0) pick_insert(L.pick[nxt], s, b);
+        } else {
+          const uint64_t bk = hh ? best[1] : best[0];
+          const unsigned long long c = hh ? mc[1] : mc[0], p = hh ? mp[1] : mp[0], r = hh ? mr[1] : mr[0];
+          const int sm_ = hh ? sum[1] : sum[0];
+          const uint32_t fl = L.pod[b].flags;
+          const int feasible = L.feas[b] + sm_;
+          {
+            const bool perr = (fl & KPF_PREFILTER_ERROR) != 0 || na_prescore_error(fl, feasible);
+            const int32_t sel = (feasible > 0 && bk && !perr) ? (int32_t)(bk & 0xFFFFFull) : -1;
+            int32_t org = -1;
+            if (c) org = 64 + b * 64 + (__ffsll((long long)c) - 1);
+            else if (p) org = __ffsll((long long)p) - 1;
+            else if (r) org = L.O[cur][__ffsll((long long)r) - 1];
+            L.S[nxt][b] = sel;
+            L.O[nxt][b] = sel >= 0 ? org : -1;
+            if (sel >= 0) pick_insert(L.pick[nxt], sel, b);
+            SumLite& sm = L.sum[b];
+            sm.best_key = sel >= 0 ? (feasible == 1 ? (bk & 0xFFFFFFFFFFull) : bk) : 0;
+            sm.selected = sel;
+            sm.feasible = feasible;
+            sm.status = perr ? 2 : (sel >= 0 ? 0 : 1);
+          }
         }
-        continue;
-      }
-      const bool pact = lane < np && L.pf[lane & 31] >= b;
-      const uint64_t kc = L.kc[b][lane];
-      const uint64_t kp = pact ? L.pkey[b][lane & 31] : 0;
-      const uint64_t kr = lane < b ? L.rk[b][lane & 31] : 0;
-      const int df = (pact ? (int)L.pdf[b][lane & 31] : 0) + (lane < b ? (int)L.rdf[b][lane & 31] : 0);
-      const uint64_t best = wave_max(max3u(kc, kp, kr));
-      int feasible;
-      bool fb = false;
-      if (STAT) {  // feasible and achiever counts in one reduction (per lane each change is in [-2, 2])
-        const int dT = (pact ? (int)L.pdfT[b][lane & 31] : 0) + (lane < b ? (int)L.rdfT[b][lane & 31] : 0);
-        const int dA = (pact ? (int)L.pdfA[b][lane & 31] : 0) + (lane < b ? (int)L.rdfA[b][lane & 31] : 0);
-        const int sum = wave_sum((df + 2) | ((dT + 2) << 10) | ((dA + 2) << 20));
-        feasible = L.feas[b] + (sum & 1023) - 128;
-        const int achT = L.achT[b] + ((sum >> 10) & 1023) - 128, achA = L.achA[b] + ((sum >> 20) & 1023) - 128;
-        const bool na_on = F.pos_na >= 0 && !(L.pod[b].flags & KPF_SKIP_NA_SCORE);
-        fb = !(L.pod[b].flags & KPF_PREFILTER_ERROR) && !na_prescore_error(L.pod[b].flags, feasible) && feasible > 0 &&
-             ((F.pos_taint >= 0 && achT <= 0) || (na_on && achA <= 0));
-      } else {
-        feasible = L.feas[b] + wave_sum(df);
-      }
-      const bool perr = (L.pod[b].flags & KPF_PREFILTER_ERROR) != 0 || na_prescore_error(L.pod[b].flags, feasible);
-      const int32_t sel = (feasible > 0 && best && !perr) ? (int32_t)(best & 0xFFFFFull) : -1;
-      const unsigned long long mc = __ballot(best && kc == best), mp = __ballot(best && kp == best),
-                               mr = __ballot(best && kr == best);
-      if (STAT && lane == 0) L.fbf[b] = fb ? 1 : 0;
-      if (fb) continue;  // win_exact_select below
-      if (lane == 0) {
-        if (STAT) {
-          L.xmt[b] = L.mt[b] < 0 ? 0 : L.mt[b];
-          L.xma[b] = (F.pos_na < 0 || (L.pod[b].flags & KPF_SKIP_NA_SCORE) || L.ma[b] < 0) ? 0 : L.ma[b];
-        }
-        int32_t org = -1;
-        if (mc) org = 64 + b * 64 + (__ffsll((long long)mc) - 1);
-        else if (mp) org = __ffsll((long long)mp) - 1;
-        else if (mr) org = L.O[cur][__ffsll((long long)mr) - 1];
-        L.S[nxt][b] = sel;
-        L.O[nxt][b] = sel >= 0 ? org : -1;
-        if (sel >= 0) pick_insert(L.pick[nxt], sel, b);
-        SumLite& sm = L.sum[b];
-        sm.best_key = sel >= 0 ? (feasible == 1 ? (best & 0xFFFFFFFFFFull) : best) : 0;
-        sm.selected = sel;
-        sm.feasible = feasible;
-        sm.status = perr ? 2 : (sel >= 0 ? 0 : 1);
       }
     }
     if (iters == 0) STAMP(23);
@@ -4910,12 +5058,18 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
     }
     if (iters < 2) STAMP(19 + iters);
     ++iters;
+    bool changed;
     {  // every wave derives the same stable prefix
       const int32_t so = L.S[cur][lane & 31], sn = L.S[nxt][lane & 31];
       unsigned long long m = __ballot(lane < nb && lane >= stable && sn != so);
       stable = m ? min(__ffsll((long long)m), nb) : nb;
+      changed = m != 0;
     }
     cur = nxt;
+    if (!changed) break;  // (S[nxt] == S[cur]: the row table stands for the final picks)
+    // (also when only the last pod's pick changed, which ends the iteration: P_W is copied from the table)
+    win_fill_rows<PER>(C, L, A, L.S[cur], L.O[cur], nb, stable, R, tid);
+    lds_barrier();
     if (stable >= nb) break;
   }
   STAMP(4);
@@ -4964,24 +5118,18 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
   // blocks of window W+2 wait for it), then summaries and per-pair patches
   const PickTab& T = L.pick[cur];
   if (wave == 0) {  // P_W: each node picked in the window, by its last pick
+    // (copied from the row table: base is the origin's start row, after the row
+    // under every pick of the node)
     const int a = lane;
-    const int32_t Sv = a < nb ? L.S[cur][a] : -1;
-    int h = Sv >= 0 ? tab_find(T.node, Sv) : -1;
-    const bool last = h >= 0 && T.last[h] == a;
+    const PickRow& e = L.pr[a & 31];
+    const bool last = a < nb && e.node >= 0 && e.nx == KSG_BATCH;
     unsigned long long m = __ballot(last);
     if (last) {
-      Delta cum;
-      delta_of(L.pod[a], cum);
-      int nx;
-      if (T.cnt[h] > 1) pick_chain(L, L.S[cur], a, Sv, cum, nx);
-      RowV st, snap;
-      origin_rows<PER>(C, L, A, L.O[cur][a], st, snap);
       Pend p;
-      p.node = Sv;
+      p.node = e.node;
       p.pad = 0;
-      p.base = st;
-      apply_delta(st, cum, R);
-      p.after = st;
+      p.base = e.base;
+      p.after = e.after;
       st_obj<PER>(A.pnext + __popcll(m & ((1ull << a) - 1)), p);
     }
     if (lane == 0) stv<PER>(A.pnext_n, (int32_t)__popcll(m));
