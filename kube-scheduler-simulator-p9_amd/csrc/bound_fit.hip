@@ -7,24 +7,21 @@
 //   k_bound_fit<false>  the (node tile x pod tile) grid of snapshot_query.hip
 //                 over the bound pods: sq_rows' rows, the gate sq_live.  A pod's
 //                 program lies in the victim store (its offset and the pod's own
-//                 local node index are wave-uniform reads, like its header and
-//                 requests).  The profile is walked in order, sq_walk<kPmBoundFit>
-//                 -- NodeName left out, a bound pod's spec.nodeName is its
-//                 placement -- and NodeResourcesFit is fit_filter, the one body
-//                 every kernel runs, over a register source: allocatable() is
-//                 free_r, requested() 0, allowed() left, podcnt() 0.  On the one
-//                 lane whose node is the pod's own the source holds free_r +
-//                 request_r and left + 1: the rows with the pod taken off them.
+//                 local node index are wave-uniform reads, like sq_pod's).  The
+//                 profile is walked in order, sq_walk<kPmPlaced>, and
+//                 NodeResourcesFit is fit_filter, the one body every kernel runs,
+//                 over the register source SqLeft.  On the one lane whose node is
+//                 the pod's own the source holds free_r + request_r and left + 1:
+//                 the rows with the pod taken off them.
 //   k_bound_fit<true>   the same body for one pod with a store of the code per node
 //                 (ksg_bound_fit_nodes).
 //   k_bound_fit_init    presets the structs: {node, KSG_FILTER_NOT_EVALUATED, 0, 0xFFFFFFFF}.
 //   k_node_evict  one thread per bound pod over the finished structs, three
 //                 atomicAdds into its node's row (ksg_node_evictability).
 //
-// Accumulation, all integer: per wave other_nodes is ballots and popcounts, and
-// the lowest passing node of the wave is read off the ballots (the lowest k with
-// a set bit, its lowest lane: a lane's nodes ascend with k); lane 0 adds / mins
-// them into the block's LDS pair of the pod; after the last pod the block issues
+// Accumulation, all integer: sq_first gives the wave's count of passing nodes and
+// the lowest of them off one ballot per slot; lane 0 adds / mins them into the
+// block's LDS pair of the pod; after the last pod the block issues
 // one global atomicAdd and one atomicMin per pod with a passing node.  own_code
 // is a plain store by the one lane of the grid whose node is the pod's own.  The
 // answer does not depend on the order in which waves and blocks arrive.
@@ -36,26 +33,10 @@ namespace ksg {
 
 using BoundFit = struct ::ksg_bound_fit;  // (the function of the same name hides the struct's)
 using NodeEvict = struct ::ksg_node_evict;
-constexpr uint32_t kPmBoundFit = (1u << KP_TAINT) | (1u << KP_NA) | (1u << KP_UNSCHED);
 static_assert(sizeof(BoundFit) == 16 && offsetof(BoundFit, own_code) == 4 && offsetof(BoundFit, other_nodes) == 8 &&
                   offsetof(BoundFit, first_other) == 12,
               "the kernel accumulates into the struct's own layout");
 static_assert(sizeof(NodeEvict) == 16 && offsetof(NodeEvict, stuck) == 4 && offsetof(NodeEvict, drifted) == 8, "");
-
-// fit_filter's pod: the flags and the requests on the cluster's columns (0 beyond them)
-struct BfPod {
-  uint32_t flags;
-  int64_t req[KSG_MAX_RES];
-};
-// fit_filter's operand source over a node row held in registers, as what is left of it
-struct BfSrc {
-  const int64_t (&fr)[KSG_MAX_RES];
-  int32_t left;
-  __device__ __forceinline__ int64_t allocatable(int res) const { return fr[res]; }
-  __device__ __forceinline__ int64_t requested(int) const { return 0; }
-  __device__ __forceinline__ int32_t podcnt() const { return 0; }
-  __device__ __forceinline__ int32_t allowed() const { return left; }
-};
 
 __global__ __launch_bounds__(256) void k_bound_fit_init(const int32_t* __restrict__ own, uint32_t goff, uint32_t count,
                                                         BoundFit* out) {
@@ -93,13 +74,8 @@ __global__ __launch_bounds__(256) void k_bound_fit(DevCluster C, DevProfile F, c
     const uint32_t j = blockIdx.y * kSqPods + pi;
     if (j >= count) break;  // (block-uniform)
     const ProgView V = view(store + off[j]);
-    const ksg_prog* h = V.h;
-    const uint32_t flags = h->flags;
     const uint32_t o = (uint32_t)own[j];  // (0xFFFFFFFF: its node is not in the snapshot; no lane holds it)
-    BfPod pod;
-    pod.flags = flags;
-#pragma unroll
-    for (uint32_t r = 0; r < KSG_MAX_RES; ++r) pod.req[r] = r < C.R ? h->req[r] : 0;
+    const SqPod pod = sq_pod(C, V.h);
     uint32_t code[kSqNpt];
 #pragma unroll
     for (uint32_t k = 0; k < kSqNpt; ++k) {
@@ -110,8 +86,8 @@ __global__ __launch_bounds__(256) void k_bound_fit(DevCluster C, DevProfile F, c
         int64_t f[KSG_MAX_RES];
 #pragma unroll
         for (uint32_t r = 0; r < KSG_MAX_RES; ++r) f[r] = fr[k][r] + (home ? pod.req[r] : 0);
-        const BfSrc src{f, left[k] + (home ? 1 : 0)};
-        code[k] = sq_walk<kPmBoundFit>(C, F, V, n, [&] { return fit_filter(src, &pod, (uint32_t)KSG_MAX_RES); });
+        const SqLeft src{f, left[k] + (home ? 1 : 0)};
+        code[k] = sq_walk<kPmPlaced>(C, F, V, n, [&] { return fit_filter(src, &pod, (uint32_t)KSG_MAX_RES); });
       }
     }
     if (PER_NODE) {
@@ -123,17 +99,15 @@ __global__ __launch_bounds__(256) void k_bound_fit(DevCluster C, DevProfile F, c
       continue;
     }
     // the wave's share of pod j, then lane 0 into the block's pair
-    uint32_t n_pass = 0, first = 0xFFFFFFFFu;
+    SqBallot pass[kSqNpt];
 #pragma unroll
     for (uint32_t k = 0; k < kSqNpt; ++k) {
       const uint32_t n = base + k * 256;
       if (n == o) out[j].own_code = code[k];  // (n < C.N: o is a local node; one lane of the grid)
-      const unsigned long long b = __ballot(code[k] == KSG_FILTER_PASS && n != o);
-      if (!b) continue;  // (wave-uniform)
-      n_pass += (uint32_t)__popcll(b);
-      if (first == 0xFFFFFFFFu)
-        first = C.goff + blockIdx.x * kSqTile + (threadIdx.x & ~63u) + k * 256 + (uint32_t)__ffsll((long long)b) - 1;
+      pass[k] = __ballot(code[k] == KSG_FILTER_PASS && n != o);
     }
+    uint32_t n_pass;
+    const uint32_t first = sq_first(C.goff + blockIdx.x * kSqTile, pass, &n_pass);
     if (n_pass && lane0()) {
       atomicAdd(&acc[pi][0], n_pass);
       atomicMin(&acc[pi][1], first);
@@ -173,10 +147,7 @@ int bound_fit_run(Engine& eng, uint32_t first, uint32_t count, const int32_t* ow
                   std::string& err) {
   Engine::Impl& I = *eng.impl();
   const uint32_t N = I.N;
-  if (!I.F.n || I.F.pos_fit < 0) {  // (host.cpp checked the profile; the kernel reads a Fit profile)
-    err = "bound_fit: NodeResourcesFit is not in the profile";
-    return KSG_E_INVALID;
-  }
+  if (!sq_need_fit(I, "bound_fit", err)) return KSG_E_INVALID;
   if ((size_t)first + count > I.vstore_off.size()) {  // (host.cpp ensured the store for this very bound list)
     err = "bound_fit: bound pod outside the victim store";
     return KSG_E_STATE;
@@ -187,20 +158,18 @@ int bound_fit_run(Engine& eng, uint32_t first, uint32_t count, const int32_t* ow
   const size_t back_bytes = evict || per_node ? row_bytes : fit_bytes;  // what crosses the host link
   if (!back_bytes) return KSG_OK;
   // the launch inputs: every pod's offset into the store, then its own local node
-  const size_t in_bytes = (size_t)count * (sizeof(uint64_t) + sizeof(int32_t));
-  std::vector<uint8_t> in(in_bytes);
-  {
-    uint64_t* o64 = reinterpret_cast<uint64_t*>(in.data());
-    for (uint32_t i = 0; i < count; ++i) o64[i] = I.vstore_off[(size_t)first + i];
-    if (count) std::memcpy(in.data() + (size_t)count * sizeof(uint64_t), own + first, (size_t)count * sizeof(int32_t));
+  SqIn in;
+  const size_t at_off = in.add<uint64_t>(count), at_own = in.add<int32_t>(count);
+  in.stage();
+  if (count) {
+    std::memcpy(in.host<uint64_t>(at_off), I.vstore_off.data() + first, (size_t)count * sizeof(uint64_t));
+    std::memcpy(in.host<int32_t>(at_own), own + first, (size_t)count * sizeof(int32_t));
   }
-  if (!I.bf_in.alloc(in_bytes, err) || !I.hr_dev.alloc(fit_bytes + row_bytes, err)) return KSG_E_DEVICE;
-  const uint64_t* d_off = reinterpret_cast<const uint64_t*>(I.bf_in.p);
-  const int32_t* d_own = reinterpret_cast<const int32_t*>(I.bf_in.p + (size_t)count * sizeof(uint64_t));
-  BoundFit* d_fit = reinterpret_cast<BoundFit*>(I.hr_dev.p);
-  uint8_t* d_row = I.hr_dev.p + fit_bytes;
   auto enqueue = [&](hipStream_t s) -> bool {
-    if (in_bytes) HIPCHK(hipMemcpyAsync(I.bf_in.p, in.data(), in_bytes, hipMemcpyHostToDevice, s));
+    const uint64_t* d_off = in.dev<const uint64_t>(at_off);
+    const int32_t* d_own = in.dev<const int32_t>(at_own);
+    BoundFit* d_fit = reinterpret_cast<BoundFit*>(I.sq_out.p);
+    uint8_t* d_row = I.sq_out.p + fit_bytes;
     if (per_node) {
       hipLaunchKernelGGL(k_bound_fit<true>, dim3((N + kSqTile - 1) / kSqTile), dim3(256), 0, s, I.cluster(), I.F,
                          I.vstore.p, d_off, d_own, 1u, (BoundFit*)nullptr, reinterpret_cast<uint32_t*>(d_row));
@@ -221,9 +190,9 @@ int bound_fit_run(Engine& eng, uint32_t first, uint32_t count, const int32_t* ow
     }
     return true;
   };
-  if (!sq_fetch(I, evict || per_node ? d_row : I.hr_dev.p, back_bytes, enqueue, err)) return KSG_E_DEVICE;
-  std::memcpy(per_node ? (void*)bo.codes : evict ? (void*)bo.evict : (void*)bo.fit, I.sq_host.p, back_bytes);
-  return KSG_OK;
+  void* dst = per_node ? (void*)bo.codes : evict ? (void*)bo.evict : (void*)bo.fit;
+  const size_t back_at = evict || per_node ? fit_bytes : 0;
+  return sq_fetch(I, &in, fit_bytes + row_bytes, back_at, back_bytes, dst, enqueue, err) ? KSG_OK : KSG_E_DEVICE;
 }
 }  // namespace
 

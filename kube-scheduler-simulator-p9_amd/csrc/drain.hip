@@ -8,17 +8,20 @@
 //                 indices and victim-store offsets, ascending bound index) are
 //                 taken in order.  For a subject the block walks the nodes in
 //                 ascending tiles of kSqTile: a lane computes the codes of its
-//                 kSqNpt nodes as k_bound_fit does (sq_live, sq_walk<kPmBoundFit>,
-//                 fit_filter over the register source free_r / left), the source
-//                 lowered by the overlay's entry for the node if it has one; x
-//                 itself is no destination.  The wave's lowest passing node is
-//                 read off the ballots, one LDS atomicMin per wave gives the
-//                 tile's, and after a barrier every thread reads it.  The walk
-//                 ends at the first tile with a hit: first fit costs a loose
-//                 cluster one tile per subject, not N nodes.  Thread 0 then
-//                 counts the subject on its destination in the overlay, and the
-//                 block barriers.  At the end thread 0 stores the 32-byte struct:
-//                 nothing is accumulated across blocks.
+//                 kSqNpt nodes as k_bound_fit does, the source lowered by the
+//                 overlay's entry for the node if it has one; x itself is no
+//                 destination.  The tile's lowest passing node comes off the
+//                 ballots and through the three rotating LDS words as sq_first
+//                 and SqFirstHit::step (snapshot_query.hip) do it, one barrier
+//                 per tile step, written out here: called from this kernel they
+//                 give the same answers, but the listing moves throughout and
+//                 ksg_drain measured 2.5 to 6 % slower on loose clusters.  The
+//                 walk ends at the first tile with a hit: first fit costs a loose
+//                 cluster one tile per subject, not N nodes.  The rows are loaded
+//                 when the walk enters another tile than the one the registers
+//                 hold.  Thread 0 then counts the subject on its destination in
+//                 the overlay, and the block barriers.  At the end thread 0
+//                 stores the 32-byte struct: nothing is accumulated across blocks.
 //   k_drain<true>   the same body for one candidate with a store of {bound, dest}
 //                 per subject (ksg_drain_plan); subjects beyond the cap get -2.
 //
@@ -32,22 +35,11 @@
 // is left, so a node that fails without it fails with it.  Not tuned: see
 // DESIGN.md "Drain simulation".
 //
-// The tile's rows are loaded when the walk enters another tile than the one the
-// registers hold, so subjects that all hit in tile 0 load it once.
-//
-// The tile's lowest hit goes through three LDS words used in rotation, a running
-// count `it` of tile steps choosing word it % 3: the waves min into it before the
-// step's barrier, every thread reads it after the barrier, and thread 0 then
-// presets word (it + 2) % 3 -- last read before this barrier, next written
-// after the following one.  One barrier per tile step.
-//
-// Forward progress: the only waits are block barriers that every thread
-// reaches.  The subject loop's bound, the tile loop's bound and the found-break
-// are block-uniform: the subject count and the tile's hit are read from LDS
-// after a barrier, the tile count is a kernel argument.  No thread waits on
-// another block.  No loop is unbounded: subjects <= KSG_DRAIN_MAX, tiles <=
-// ceil(N / kSqTile), the overlay search <= the subjects so far, the profile walk
-// as in snapshot_query.hip.  The loops hold no return.
+// Forward progress: snapshot_query.hip's argument.  The subject loop's bound, the
+// tile loop's bound and the found-break are block-uniform: the subject count and
+// the tile's hit are read from LDS after a barrier, the tile count is a kernel
+// argument.  Subjects <= KSG_DRAIN_MAX, tiles <= ceil(N / kSqTile), the overlay
+// search <= the subjects so far.
 #include "../../include/ksg.h"
 
 namespace ksg {
@@ -101,7 +93,7 @@ __global__ __launch_bounds__(256) void k_drain(DevCluster C, DevProfile F, const
   for (uint32_t s = 0; s < n_sim; ++s) {
     const ProgView V = view(store + off[start + s]);
     const ksg_prog* h = V.h;
-    BfPod pod;
+    SqPod pod;
     pod.flags = h->flags;
 #pragma unroll
     for (uint32_t r = 0; r < KSG_MAX_RES; ++r) pod.req[r] = r < C.R ? h->req[r] : 0;
@@ -120,15 +112,15 @@ __global__ __launch_bounds__(256) void k_drain(DevCluster C, DevProfile F, const
         const uint32_t n = base + k * 256;
         bool pass = false;
         if (n != x && sq_live(C, V, n)) {
-          const uint32_t code = sq_walk<kPmBoundFit>(C, F, V, n, [&]() -> uint32_t {
-            const uint32_t alone = fit_filter(BfSrc{fr[k], left[k]}, &pod, (uint32_t)KSG_MAX_RES);
+          const uint32_t code = sq_walk<kPmPlaced>(C, F, V, n, [&]() -> uint32_t {
+            const uint32_t alone = fit_filter(SqLeft{fr[k], left[k]}, &pod, (uint32_t)KSG_MAX_RES);
             if (alone) return alone;
             for (uint32_t j = 0; j < nd; ++j) {
               if (ov_dest[j] != n) continue;
               int64_t f[KSG_MAX_RES];
 #pragma unroll
               for (uint32_t r = 0; r < KSG_MAX_RES; ++r) f[r] = fr[k][r] - ov_req[j][r];
-              return fit_filter(BfSrc{f, left[k] - ov_cnt[j]}, &pod, (uint32_t)KSG_MAX_RES);
+              return fit_filter(SqLeft{f, left[k] - ov_cnt[j]}, &pod, (uint32_t)KSG_MAX_RES);
             }
             return 0;
           });
@@ -138,6 +130,7 @@ __global__ __launch_bounds__(256) void k_drain(DevCluster C, DevProfile F, const
         if (b && first == 0xFFFFFFFFu)  // (wave-uniform; a lane's nodes ascend with k)
           first = t * kSqTile + k * 256 + (tid & ~63u) + (uint32_t)__ffsll((long long)b) - 1;
       }
+      // (keep in step with SqFirstHit::step, snapshot_query.hip, which carries the argument; sq_first above)
       if (first != 0xFFFFFFFFu && lane0()) atomicMin(&hit[it % 3], first);
       __syncthreads();
       found = hit[it % 3];
@@ -192,10 +185,7 @@ namespace {
 int drain_run(Engine& eng, const DrainIn& in, Drain* out, DrainMove* plan, std::string& err) {
   Engine::Impl& I = *eng.impl();
   const uint32_t N = I.N;
-  if (!I.F.n || I.F.pos_fit < 0) {  // (host.cpp checked the profile; the kernel reads a Fit profile)
-    err = "drain: NodeResourcesFit is not in the profile";
-    return KSG_E_INVALID;
-  }
+  if (!sq_need_fit(I, "drain", err)) return KSG_E_INVALID;
   const uint32_t total = in.start[in.count];
   if ((size_t)in.first_node + in.count > N || (plan && in.count != 1)) {
     err = "drain: candidates outside the snapshot";
@@ -204,42 +194,37 @@ int drain_run(Engine& eng, const DrainIn& in, Drain* out, DrainMove* plan, std::
   const size_t back_bytes = plan ? (size_t)total * sizeof(DrainMove) : (size_t)in.count * sizeof(Drain);
   if (!back_bytes) return KSG_OK;
   // the launch inputs: the subjects' store offsets, the candidates, the subjects' bound indices
-  const size_t off_bytes = (size_t)total * sizeof(uint64_t), cand_bytes = (size_t)in.count * sizeof(DrainCand);
-  const size_t in_bytes = off_bytes + cand_bytes + (size_t)total * sizeof(int32_t);
-  std::vector<uint8_t> host(in_bytes);
-  {
-    uint64_t* o64 = reinterpret_cast<uint64_t*>(host.data());
-    DrainCand* hc = reinterpret_cast<DrainCand*>(host.data() + off_bytes);
-    for (uint32_t i = 0; i < total; ++i) {
-      const int32_t b = in.subj[i];
-      if (b < 0 || (size_t)b >= I.vstore_off.size()) {  // (host.cpp ensured the store for this very bound list)
-        err = "drain: bound pod outside the victim store";
-        return KSG_E_STATE;
-      }
-      o64[i] = I.vstore_off[(size_t)b];
+  SqIn li;
+  const size_t at_off = li.add<uint64_t>(total), at_cand = li.add<DrainCand>(in.count), at_bidx = li.add<int32_t>(total);
+  li.stage();
+  uint64_t* h_off = li.host<uint64_t>(at_off);
+  DrainCand* h_cand = li.host<DrainCand>(at_cand);
+  if (total) std::memcpy(li.host<int32_t>(at_bidx), in.subj, (size_t)total * sizeof(int32_t));
+  for (uint32_t i = 0; i < total; ++i) {
+    const int32_t b = in.subj[i];
+    if (b < 0 || (size_t)b >= I.vstore_off.size()) {  // (host.cpp ensured the store for this very bound list)
+      err = "drain: bound pod outside the victim store";
+      return KSG_E_STATE;
     }
-    for (uint32_t c = 0; c < in.count; ++c)
-      hc[c] = DrainCand{in.start[c], in.start[c + 1] - in.start[c], in.pods[c], in.daemon[c]};
-    if (total) std::memcpy(host.data() + off_bytes + cand_bytes, in.subj, (size_t)total * sizeof(int32_t));
+    h_off[i] = I.vstore_off[(size_t)b];
   }
-  if (!I.bf_in.alloc(in_bytes, err) || !I.hr_dev.alloc(back_bytes, err)) return KSG_E_DEVICE;
-  const uint64_t* d_off = reinterpret_cast<const uint64_t*>(I.bf_in.p);
-  const DrainCand* d_cand = reinterpret_cast<const DrainCand*>(I.bf_in.p + off_bytes);
-  const int32_t* d_bidx = reinterpret_cast<const int32_t*>(I.bf_in.p + off_bytes + cand_bytes);
+  for (uint32_t c = 0; c < in.count; ++c)
+    h_cand[c] = DrainCand{in.start[c], in.start[c + 1] - in.start[c], in.pods[c], in.daemon[c]};
   const uint32_t cap = std::min(I.drain_max, kDrainMax), tiles = (N + kSqTile - 1) / kSqTile;
   auto enqueue = [&](hipStream_t s) -> bool {
-    HIPCHK(hipMemcpyAsync(I.bf_in.p, host.data(), in_bytes, hipMemcpyHostToDevice, s));
+    const DrainCand* d_cand = li.dev<const DrainCand>(at_cand);
+    const uint64_t* d_off = li.dev<const uint64_t>(at_off);
+    const int32_t* d_bidx = li.dev<const int32_t>(at_bidx);
     if (plan)
       hipLaunchKernelGGL(k_drain<true>, dim3(1), dim3(256), 0, s, I.cluster(), I.F, I.vstore.p, d_cand, d_off, d_bidx,
-                         in.first_node, cap, tiles, (Drain*)nullptr, reinterpret_cast<DrainMove*>(I.hr_dev.p));
+                         in.first_node, cap, tiles, (Drain*)nullptr, reinterpret_cast<DrainMove*>(I.sq_out.p));
     else
       hipLaunchKernelGGL(k_drain<false>, dim3(in.count), dim3(256), 0, s, I.cluster(), I.F, I.vstore.p, d_cand, d_off,
-                         d_bidx, in.first_node, cap, tiles, reinterpret_cast<Drain*>(I.hr_dev.p), (DrainMove*)nullptr);
+                         d_bidx, in.first_node, cap, tiles, reinterpret_cast<Drain*>(I.sq_out.p), (DrainMove*)nullptr);
     return true;
   };
-  if (!sq_fetch(I, I.hr_dev.p, back_bytes, enqueue, err)) return KSG_E_DEVICE;
-  std::memcpy(plan ? (void*)plan : (void*)out, I.sq_host.p, back_bytes);
-  return KSG_OK;
+  void* dst = plan ? (void*)plan : (void*)out;
+  return sq_fetch(I, &li, back_bytes, 0, back_bytes, dst, enqueue, err) ? KSG_OK : KSG_E_DEVICE;
 }
 }  // namespace
 

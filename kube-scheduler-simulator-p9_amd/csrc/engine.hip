@@ -5725,17 +5725,14 @@ struct Engine::Impl {
   // word, keys, counts)
   uint32_t diag_slots = kDiagMax;
   DBuf<uint8_t> dg_tab;
-  // headroom (headroom.hip): the device result structs (or one pod's node row)
-  DBuf<uint8_t> hr_dev;
-  // eviction fit (bound_fit.hip): a launch's inputs, the bound pods' store offsets and own nodes
-  // (its results use headroom's device block: the context lock serialises the calls)
-  DBuf<uint8_t> bf_in;
+  // placement queries (snapshot_query.hip: headroom, eviction fit, drain, scale-up): a call's launch
+  // inputs and its answer on the device (the context lock serialises the calls)
+  DBuf<uint8_t> sq_in, sq_out;
   // drain simulation (drain.hip): subjects simulated per candidate at most (KSG_DRAIN_MAX: a power of
-  // two in [2, kDrainMax]; tests reach the cap with a handful of pods); its launch inputs use bf_in and
-  // its results hr_dev
+  // two in [2, kDrainMax]; tests reach the cap with a handful of pods)
   uint32_t drain_max = kDrainMax;
   // scale-up simulation (scale_up.hip): the upper bound of max_nodes (KSG_SCALE_MAX: a power of two in
-  // [2, kScaleMax]); its launch inputs and the open bytes use bf_in and its results hr_dev
+  // [2, kScaleMax])
   uint32_t scale_max = kScaleMax;
   PinnedBlock sq_host;  // the pinned block every snapshot query's answer crosses in
   DBuf<int32_t> knorm;   // normalized scores of one kept pod

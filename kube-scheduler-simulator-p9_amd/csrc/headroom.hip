@@ -32,7 +32,6 @@ namespace ksg {
 
 using Headroom = struct ::ksg_headroom;  // (the function of the same name hides the struct's)
 constexpr uint32_t kHrWords = sizeof(Headroom) / 4;
-constexpr uint32_t kPmHeadroom = (1u << KP_TAINT) | (1u << KP_NA) | (1u << KP_UNSCHED) | (1u << KP_NODENAME);
 static_assert(KSG_HEADROOM_BOUNDS == 1 + KSG_MAX_RES, "bound[]: the pod room, then every resource column");
 static_assert(sizeof(Headroom) == 64 && offsetof(Headroom, nodes) == 8 && offsetof(Headroom, open_nodes) == 12 &&
                   offsetof(Headroom, max_node) == 16 && offsetof(Headroom, best_node) == 20 &&
@@ -169,30 +168,24 @@ int headroom_run(Engine& eng, uint32_t first, uint32_t count, void* user, std::s
   const HeadroomCall& hc = *static_cast<const HeadroomCall*>(user);
   const bool per_node = hc.out_nodes != nullptr;
   const uint32_t N = I.N;
-  if (!I.F.n || I.F.pos_fit < 0) {  // (host.cpp checked the profile; the kernel reads a Fit profile)
-    err = "headroom: NodeResourcesFit is not in the profile";
-    return KSG_E_INVALID;
-  }
+  if (!sq_need_fit(I, "headroom", err)) return KSG_E_INVALID;
   const size_t bytes = per_node ? (size_t)N * sizeof(int32_t) : (size_t)count * sizeof(Headroom);
   if (!bytes) return KSG_OK;
   auto enqueue = [&](hipStream_t s) -> bool {
     if (per_node) {
       hipLaunchKernelGGL(k_headroom<true>, dim3((N + kSqTile - 1) / kSqTile), dim3(256), 0, s, I.cluster(), I.F, I.progs.p,
-                         I.prog_off_d.p, first, 1u, (Headroom*)nullptr, reinterpret_cast<int32_t*>(I.hr_dev.p));
+                         I.prog_off_d.p, first, 1u, (Headroom*)nullptr, reinterpret_cast<int32_t*>(I.sq_out.p));
       return true;
     }
-    HIPCHK(hipMemsetAsync(I.hr_dev.p, 0, bytes, s));
+    HIPCHK(hipMemsetAsync(I.sq_out.p, 0, bytes, s));
     sq_chunks(N, count, [&](uint32_t c0, uint32_t cn, dim3 grid) {
       hipLaunchKernelGGL(k_headroom<false>, grid, dim3(256), 0, s, I.cluster(), I.F, I.progs.p, I.prog_off_d.p, first + c0,
-                         cn, reinterpret_cast<Headroom*>(I.hr_dev.p) + c0, (int32_t*)nullptr);
+                         cn, reinterpret_cast<Headroom*>(I.sq_out.p) + c0, (int32_t*)nullptr);
     });
     return true;
   };
-  if (!I.hr_dev.alloc(bytes, err) || !sq_fetch(I, I.hr_dev.p, bytes, enqueue, err)) return KSG_E_DEVICE;
-  if (per_node) {
-    std::memcpy(hc.out_nodes, I.sq_host.p, bytes);
-    return KSG_OK;
-  }
+  if (!sq_fetch(I, nullptr, bytes, 0, bytes, hc.out_nodes, enqueue, err)) return KSG_E_DEVICE;
+  if (per_node) return KSG_OK;
   for (uint32_t i = 0; i < count; ++i) {  // the key back into its two fields
     Headroom hr;
     std::memcpy(&hr, I.sq_host.p + (size_t)i * sizeof(hr), sizeof(hr));

@@ -5680,8 +5680,8 @@ int ksg_node_nonzero(ksg_ctx* ctx, int64_t* nonzero, uint32_t n) {
 
 }  // extern "C"
 
-// The context's side of the snapshot queries (engine.h: kept_pod_call, diag_call,
-// headroom_call, bound_fit_call; DESIGN.md "Snapshot queries").
+// The context's side of the snapshot queries (engine.h: the *_call functions;
+// DESIGN.md "Snapshot queries").
 namespace ksg {
 namespace {
 enum : int {
@@ -5690,15 +5690,15 @@ enum : int {
 };
 // What every snapshot query begins with: the lock (held in lk from here on), the
 // guard, then in this order the refusal of sharded contexts and of a profile
-// outside the closed form (KSG_E_INVALID), and the argument / range check: pods
-// [.., end) against limit(c) and, with n_nodes, the caller's node count against
-// the local one (KSG_E_RANGE).  what: the entry point's name.  KSG_OK: go on.
+// outside the closed form (KSG_E_INVALID), and the argument / range check: [.., end)
+// against limit(c) (no limit: the call has no range) and, with n_nodes, the caller's node
+// count against the local one (KSG_E_RANGE).  what: the entry point's name.  KSG_OK: go on.
 int snapshot_gate(ksg_ctx* ctx, std::unique_lock<std::recursive_mutex>& lk, const char* what, int checks, bool args_ok,
                   uint64_t end, size_t (*limit)(const Cluster& c), const uint32_t* n_nodes = nullptr) {
   if (ctx) lk = std::unique_lock<std::recursive_mutex>(ctx->mu);
   KSG_GUARD(ctx);
   const Cluster& c = ctx->c;
-  const bool in_range = args_ok && end <= limit(c) && (!n_nodes || *n_nodes == c.hi - c.lo);
+  const bool in_range = args_ok && (!limit || end <= limit(c)) && (!n_nodes || *n_nodes == c.hi - c.lo);
   if ((checks & kGateRangeFirst) && !in_range) return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
   if (c.shards > 1) return ctx->fail(std::string(what) + ": not offered on a sharded context", KSG_E_INVALID);
   if ((checks & kGateClosedForm) && !c.headroom_refusal.empty())
@@ -5707,6 +5707,29 @@ int snapshot_gate(ksg_ctx* ctx, std::unique_lock<std::recursive_mutex>& lk, cons
   return KSG_OK;
 }
 size_t kept_limit(const Cluster& c) { return std::min(c.queue.size(), c.meta.size()); }
+size_t queue_limit(const Cluster& c) { return c.queue.size(); }
+size_t bound_limit(const Cluster& c) { return c.bound.size(); }
+size_t node_limit(const Cluster& c) { return c.hi - c.lo; }
+
+// The programs a placement query reads, ready on the device: the queue's compiled if they are not yet (as
+// ksg_whatif; KSG_E_INVALID), then the victim store -- every bound pod's program, built per snapshot generation
+// against the queue's classes, with or without DefaultPreemption -- or queue pods [first, first + count) refreshed
+// (KSG_E_DEVICE).  KSG_OK: go on.
+int programs_ready(ksg_ctx* ctx, bool store, uint32_t first = 0, uint32_t count = 0) {
+  auto& c = ctx->c;
+  if (!c.compile_queue()) return ctx->fail(c.err, KSG_E_INVALID);
+  if (store ? !c.ensure_victim_store() : !c.refresh_programs(first, count)) return ctx->fail(c.err, KSG_E_DEVICE);
+  return KSG_OK;
+}
+
+// The bound pods of local node x in ascending bound index, split by Pod::stays (a drain leaves those in place):
+// each(b, stays); boff: c.bound_by_node(), one counting sort per snapshot generation.  Returns their number.
+// (A callable, inlined: with two vectors to append to, ksg_drain lost 1 ns a subject.)
+template <class Each>
+uint32_t bound_on_node(const Cluster& c, const std::vector<uint32_t>& boff, uint32_t x, Each each) {
+  for (uint32_t e = boff[x]; e < boff[x + 1]; ++e) each(c.bcsr_idx[e], c.bound[c.bcsr_idx[e]].stays);
+  return boff[x + 1] - boff[x];
+}
 }  // namespace
 
 int kept_pod_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
@@ -5759,28 +5782,23 @@ int diag_call(ksg_ctx* ctx, uint32_t q, bool args_ok, const char* what,
 int headroom_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const uint32_t* n_nodes, const char* what,
                   int (*fn)(Engine& eng, uint32_t first, uint32_t count, void* user, std::string& err), void* user) {
   std::unique_lock<std::recursive_mutex> lk;
-  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, (uint64_t)first + count,
-                                   [](const Cluster& c) { return c.queue.size(); }, n_nodes))
+  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, (uint64_t)first + count, queue_limit, n_nodes))
     return rc;
   auto& c = ctx->c;
   if (!count) return KSG_OK;
-  if (!c.compile_queue()) return ctx->fail(c.err, KSG_E_INVALID);
-  if (!c.refresh_programs(first, count)) return ctx->fail(c.err, KSG_E_DEVICE);
+  if (const int rc = programs_ready(ctx, false, first, count)) return rc;
   return ctx->done(fn(*c.eng, first, count, user, c.err));
 }
 
 // The eviction fit: headroom's refusals (under its profiles removing a bound pod
 // changes its own node's rows only); whole: the range is every bound pod (the
-// gate sees it as the empty range, which is in range whenever the whole is).
-// The victim store is ensured whether or not DefaultPreemption is in the
-// profile: per snapshot generation the first call compiles every bound pod's
-// program (the queue's classes first: the store is built against them).  Then
+// gate checks none).  The kernels read the victim store (programs_ready).  Then
 // fn on the engine, and the codes from device to profile positions.
 int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, bool args_ok, const uint32_t* n_nodes,
                    const char* what, BoundFitFn fn, const BoundFitOut& bo) {
   std::unique_lock<std::recursive_mutex> lk;
-  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, whole ? 0 : (uint64_t)first + count,
-                                   [](const Cluster& c) { return c.bound.size(); }, n_nodes))
+  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, (uint64_t)first + count,
+                                   whole ? nullptr : bound_limit, n_nodes))
     return rc;
   auto& c = ctx->c;
   if (whole) {
@@ -5788,8 +5806,7 @@ int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, boo
     count = (uint32_t)c.bound.size();
   }
   if (!count && !whole) return KSG_OK;
-  if (!c.compile_queue()) return ctx->fail(c.err, KSG_E_INVALID);
-  if (!c.ensure_victim_store()) return ctx->fail(c.err, KSG_E_DEVICE);
+  if (const int rc = programs_ready(ctx, true)) return rc;
   const std::vector<int32_t>& own = c.bound_own_nodes();
   if (const int rc = fn(*c.eng, first, count, own.data(), bo, c.err)) return ctx->fail(c.err, rc);
   if (bo.fit)
@@ -5800,54 +5817,46 @@ int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, boo
 }
 
 // The drain simulation: the eviction fit's refusals and its store (every bound
-// pod's program).  The candidates' subjects come from the bound pods grouped by
-// node (bound_by_node: one counting sort per snapshot generation, ascending
-// bound index within a node) with the pods a drain leaves in place taken out.
-// The plan of one node is sized here, before the device is asked anything.
+// pod's program).  The candidates' subjects are their bound pods without those a
+// drain leaves in place (bound_on_node).  The plan of one node is sized here,
+// before the device is asked anything.
 int drain_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const char* what, DrainFn fn,
                struct ::ksg_drain* out, struct ::ksg_drain_move* plan, uint32_t cap, uint32_t* n_out) {
   std::unique_lock<std::recursive_mutex> lk;
-  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, (uint64_t)first + count,
-                                   [](const Cluster& c) { return (size_t)(c.hi - c.lo); }))
-    return rc;
+  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, (uint64_t)first + count, node_limit)) return rc;
   auto& c = ctx->c;
   if (!count) return KSG_OK;
-  const std::vector<uint32_t>& boff = c.bound_by_node();
   std::vector<uint32_t> start(count + 1, 0);
+  const std::vector<uint32_t>& boff = c.bound_by_node();
   std::vector<int32_t> subj, pods(count), daemon(count, 0);
   for (uint32_t i = 0; i < count; ++i) {
-    const uint32_t x = first + i;
-    pods[i] = (int32_t)(boff[x + 1] - boff[x]);
-    for (uint32_t e = boff[x]; e < boff[x + 1]; ++e) {
-      const int32_t b = c.bcsr_idx[e];
-      if (c.bound[b].stays) ++daemon[i];
+    pods[i] = (int32_t)bound_on_node(c, boff, first + i, [&](int32_t b, bool stays) {
+      if (stays) ++daemon[i];
       else subj.push_back(b);
-    }
+    });
     start[i + 1] = (uint32_t)subj.size();
   }
   if (plan) {
     *n_out = start[1];
     if (cap < start[1]) return KSG_E_NOBUF;
   }
-  if (!c.compile_queue()) return ctx->fail(c.err, KSG_E_INVALID);
-  if (!c.ensure_victim_store()) return ctx->fail(c.err, KSG_E_DEVICE);
+  if (const int rc = programs_ready(ctx, true)) return rc;
   const DrainIn in{first, count, start.data(), subj.data(), pods.data(), daemon.data()};
   return ctx->done(fn(*c.eng, in, out, plan, c.err));
 }
 
-// The scale-up simulation: the drain's refusals; the lists are checked under the
-// lock the gate took (the gate sees the empty range).  The listed queue pods'
-// programs are compiled and refreshed as headroom's; the base load of a template
-// is summed here from the bound pods grouped by node (bound_by_node, Pod::stays),
-// so the device reads no bound pod and the victim store is not needed.  fn checks
+// The scale-up simulation: the drain's refusals; the call has no range, its lists
+// are checked under the lock the gate took.  The listed queue pods' programs are
+// compiled and refreshed as headroom's; the base load of a template is summed
+// here from the bound pods a drain would leave on it (bound_on_node), so the
+// device reads no bound pod and the victim store is not needed.  fn checks
 // max_nodes against the engine's cap before anything else and answers an empty
 // template list with KSG_OK.
 int scale_up_call(ksg_ctx* ctx, const uint32_t* pods, uint32_t n_pods, const uint32_t* templates, uint32_t n_templates,
                   uint32_t max_nodes, bool args_ok, const char* what, ScaleUpFn fn, struct ::ksg_scale_up* out,
                   int32_t* plan) {
   std::unique_lock<std::recursive_mutex> lk;
-  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, 0, [](const Cluster&) { return (size_t)0; }))
-    return rc;
+  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, 0, nullptr)) return rc;
   auto& c = ctx->c;
   for (uint32_t i = 0; i < n_pods; ++i)
     if (pods[i] >= c.queue.size()) return ctx->fail(std::string(what) + ": range", KSG_E_RANGE);
@@ -5856,7 +5865,7 @@ int scale_up_call(ksg_ctx* ctx, const uint32_t* pods, uint32_t n_pods, const uin
   std::vector<int64_t> base_req((size_t)n_templates * KSG_MAX_RES, 0);
   std::vector<int32_t> base_pods(n_templates, 0);
   if (n_templates) {
-    if (!c.compile_queue()) return ctx->fail(c.err, KSG_E_INVALID);
+    if (const int rc = programs_ready(ctx, false)) return rc;  // (compiled; the listed pods are refreshed one by one)
     std::vector<uint32_t> listed(pods, pods + n_pods);
     std::sort(listed.begin(), listed.end());
     listed.erase(std::unique(listed.begin(), listed.end()), listed.end());
@@ -5864,18 +5873,15 @@ int scale_up_call(ksg_ctx* ctx, const uint32_t* pods, uint32_t n_pods, const uin
       if (!c.refresh_programs(q, 1)) return ctx->fail(c.err, KSG_E_DEVICE);
     const std::vector<uint32_t>& boff = c.bound_by_node();
     std::vector<host::i64> rq;
-    for (uint32_t i = 0; i < n_templates; ++i) {
-      const uint32_t t = templates[i];
-      for (uint32_t e = boff[t]; e < boff[t + 1]; ++e) {
-        const host::Pod& p = c.bound[c.bcsr_idx[e]];
-        if (!p.stays) continue;
+    for (uint32_t i = 0; i < n_templates; ++i)
+      bound_on_node(c, boff, templates[i], [&](int32_t b, bool stays) {
+        if (!stays) return;
         host::i64 nzc, nzm;
-        c.add_requests(p, rq, nzc, nzm);
+        c.add_requests(c.bound[b], rq, nzc, nzm);
         for (size_t r = 0; r < rq.size() && r < KSG_MAX_RES; ++r)
           base_req[(size_t)i * KSG_MAX_RES + r] = host::wadd(base_req[(size_t)i * KSG_MAX_RES + r], rq[r]);
         ++base_pods[i];
-      }
-    }
+      });
   }
   const ScaleUpIn in{pods, n_pods, templates, n_templates, max_nodes, base_req.data(), base_pods.data()};
   return ctx->done(fn(*c.eng, in, out, plan, c.err));

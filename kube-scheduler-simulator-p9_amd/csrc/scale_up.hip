@@ -6,48 +6,34 @@
 //   k_scale_open   the (pods x templates) grid, one thread per pair, fully
 //                 parallel: open(p, t) -- the pod's PreFilter neither rejected
 //                 nor failed, it has no PreFilterResult node set, with NodeName
-//                 in the profile it names no node, and sq_walk<kPmBoundFit>
-//                 (TaintToleration, NodeAffinity, NodeUnschedulable) passes on
-//                 node t -- stored as one byte per pair, row t of n_pods bytes.
+//                 in the profile it names no node, and sq_walk<kPmPlaced> passes
+//                 on node t -- stored as one byte per pair, row t of n_pods bytes.
 //   k_scale_pack<false>  one block of 256 threads per template.  Bin j lives in
-//                 the registers of thread j % 256, slot j / 256: kSqNpt = 4 slots,
-//                 1,024 bins, as what is left of them (free_r and left, sq_rows'
-//                 form), every bin initialised to the empty fresh node:
-//                 allocatable_r(t) - base_r and allowed(t) - base_pods.  A slot is
-//                 indexed by an unrolled predicated loop, never by a run-time
-//                 register index, so the bins stay out of scratch.  For each pod
-//                 in list order: a closed pod (its byte) is counted and skipped
-//                 by the whole block; otherwise the header and the requests are
-//                 read wave-uniformly, every lane tests its bins with index <=
-//                 min(nodes, cap - 1) with fit_filter (bin `nodes` is the next
-//                 fresh node, still empty), the wave's lowest admitting bin is
-//                 read off the ballots, one LDS atomicMin per wave gives the
-//                 block's, and after one barrier every thread reads it.  The
-//                 owning lane lowers its bin; a hit at index == nodes opens that
-//                 bin.  Every thread keeps `nodes` and the counts in registers
-//                 (they are block-uniform).  No hit with nodes < cap: the empty
-//                 node itself did not admit the pod (too big); with nodes == cap
-//                 the empty node is tested apart, uniformly (too big or over the
-//                 cap).  At the end thread 0 stores the 32-byte struct.
+//                 the registers of thread j % 256, slot j / 256: kSqTile bins, as
+//                 what is left of them (sq_rows' form), every bin initialised to
+//                 the empty fresh node: allocatable_r(t) - base_r and allowed(t) -
+//                 base_pods.  For each pod in list order: a closed pod (its byte)
+//                 is counted and skipped by the whole block; otherwise every lane
+//                 tests its bins with index <= min(nodes, cap - 1) with fit_filter
+//                 (bin `nodes` is the next fresh node, still empty), and the
+//                 block's lowest admitting bin is sq_first's through
+//                 SqFirstHit::step, one barrier per open pod.  The owning lane
+//                 lowers its bin; a hit at index == nodes opens that bin.  Every
+//                 thread keeps `nodes` and the counts in registers (they are
+//                 block-uniform).  No hit with nodes < cap: the empty node itself
+//                 did not admit the pod (too big); with nodes == cap the empty
+//                 node is tested apart, uniformly (too big or over the cap).  At
+//                 the end thread 0 stores the 32-byte struct.
 //   k_scale_pack<true>   the same body for one template with a store of the bin
 //                 per listed pod (ksg_scale_up_plan).
-//
-// The block's lowest hit goes through the drain's three LDS words used in
-// rotation, a running count `it` of steps choosing word it % 3: the waves min
-// into it before the step's barrier, every thread reads it after the barrier,
-// and thread 0 then presets word (it + 2) % 3 -- last read before this barrier,
-// next written after the following one.  One barrier per open pod.
 //
 // The base load is summed on the host (host.cpp scale_up_call) and arrives with
 // the launch inputs; the kernels read the queue's programs and the node columns
 // and write nothing but the open bytes and the answer.
 //
-// Forward progress: the only waits are block barriers that every thread
-// reaches.  The pod loop's bound is a kernel argument, and the skip of a closed
-// pod reads one byte at a block-uniform address, so the barrier of an open pod
-// is reached by all threads or none.  No block waits on another block.  No loop
-// is unbounded: pods <= n_pods, slots and columns are constants, the profile walk
-// as in snapshot_query.hip.  The loops hold no return.
+// Forward progress: snapshot_query.hip's argument.  The pod loop's bound is a
+// kernel argument, and the skip of a closed pod reads one byte at a block-uniform
+// address, so the barrier of an open pod is reached by all threads or none.
 #include "../../include/ksg.h"
 
 namespace ksg {
@@ -78,7 +64,7 @@ __global__ __launch_bounds__(256) void k_scale_open(DevCluster C, DevProfile F, 
   const ksg_prog* h = V.h;
   const uint32_t flags = h->flags;
   const bool ok = t < C.N && !(flags & (KPF_PREFILTER_REJECT | KPF_PREFILTER_ERROR | KPF_RESTRICT)) &&
-                  !(has_nodename && h->node_name_gid != -1) && sq_walk<kPmBoundFit>(C, F, V, t) == KSG_FILTER_PASS;
+                  !(has_nodename && h->node_name_gid != -1) && sq_walk<kPmPlaced>(C, F, V, t) == KSG_FILTER_PASS;
   open[(size_t)blockIdx.y * n_pods + i] = ok ? 1 : 0;
 }
 
@@ -93,8 +79,8 @@ __global__ __launch_bounds__(256) void k_scale_pack(DevCluster C, const uint8_t*
                                                     int32_t* plan) {
   __shared__ uint32_t hit[3];
   const uint32_t tid = threadIdx.x;
-  if (tid == 0) hit[0] = hit[1] = hit[2] = 0xFFFFFFFFu;
-  __syncthreads();
+  SqFirstHit bin_hit{hit};
+  bin_hit.init();
   const uint32_t t = tmpl[blockIdx.x];
   const uint8_t* row = open + (size_t)blockIdx.x * n_pods;
   // the empty fresh node, then every bin as a copy of it
@@ -112,7 +98,7 @@ __global__ __launch_bounds__(256) void k_scale_pack(DevCluster C, const uint8_t*
 #pragma unroll
     for (uint32_t r = 0; r < KSG_MAX_RES; ++r) fr[k][r] = e_fr[r];
   }
-  uint32_t nodes = 0, it = 0;
+  uint32_t nodes = 0;
   int32_t packed = 0, closed = 0, too_big = 0, over_cap = 0, first_unpacked = -1;  // (block-uniform)
 #pragma unroll 1
   for (uint32_t i = 0; i < n_pods; ++i) {
@@ -121,26 +107,13 @@ __global__ __launch_bounds__(256) void k_scale_pack(DevCluster C, const uint8_t*
       ++closed;
       bin = kScaleClosed;
     } else {
-      const ksg_prog* h = view(progs + prog_off[pods[i]]).h;
-      BfPod pod;
-      pod.flags = h->flags;
-#pragma unroll
-      for (uint32_t r = 0; r < KSG_MAX_RES; ++r) pod.req[r] = r < C.R ? h->req[r] : 0;
+      const SqPod pod = sq_pod(C, view(progs + prog_off[pods[i]]).h);
       const uint32_t last = nodes < cap ? nodes : cap - 1;  // the highest bin tested: the next fresh node, or the cap's last
-      uint32_t first = 0xFFFFFFFFu;
+      SqBallot pass[kSqNpt];
 #pragma unroll
-      for (uint32_t k = 0; k < kSqNpt; ++k) {
-        const uint32_t j = k * 256 + tid;
-        const bool pass = j <= last && fit_filter(BfSrc{fr[k], left[k]}, &pod, (uint32_t)KSG_MAX_RES) == 0;
-        const unsigned long long b = __ballot(pass);
-        if (b && first == 0xFFFFFFFFu)  // (wave-uniform; a lane's bins ascend with k)
-          first = k * 256 + (tid & ~63u) + (uint32_t)__ffsll((long long)b) - 1;
-      }
-      if (first != 0xFFFFFFFFu && lane0()) atomicMin(&hit[it % 3], first);
-      __syncthreads();
-      const uint32_t found = hit[it % 3];
-      if (tid == 0) hit[(it + 2) % 3] = 0xFFFFFFFFu;
-      ++it;
+      for (uint32_t k = 0; k < kSqNpt; ++k)
+        pass[k] = __ballot(k * 256 + tid <= last && fit_filter(SqLeft{fr[k], left[k]}, &pod, (uint32_t)KSG_MAX_RES) == 0);
+      const uint32_t found = bin_hit.step(sq_first(0, pass));
       if (found != 0xFFFFFFFFu) {
 #pragma unroll
         for (uint32_t k = 0; k < kSqNpt; ++k) {
@@ -152,7 +125,7 @@ __global__ __launch_bounds__(256) void k_scale_pack(DevCluster C, const uint8_t*
         if (found == nodes) ++nodes;
         ++packed;
         bin = (int32_t)found;
-      } else if (nodes < cap || fit_filter(BfSrc{e_fr, e_left}, &pod, (uint32_t)KSG_MAX_RES) != 0) {
+      } else if (nodes < cap || fit_filter(SqLeft{e_fr, e_left}, &pod, (uint32_t)KSG_MAX_RES) != 0) {
         ++too_big;  // (nodes < cap: bin `nodes`, empty, was among the tested)
         bin = kScaleTooBig;
       } else {
@@ -189,10 +162,7 @@ int scale_up_run(Engine& eng, const ScaleUpIn& in, ScaleUp* out, int32_t* plan, 
   }
   if (!in.n_templates) return KSG_OK;
   if (!out && !plan) return KSG_OK;  // (ksg_scale_up_plan of an empty list may come without a buffer: nothing to write)
-  if (!I.F.n || I.F.pos_fit < 0) {  // (host.cpp checked the profile; the kernel reads a Fit profile)
-    err = "scale_up: NodeResourcesFit is not in the profile";
-    return KSG_E_INVALID;
-  }
+  if (!sq_need_fit(I, "scale_up", err)) return KSG_E_INVALID;
   if (plan && in.n_templates != 1) {
     err = "scale_up: a plan is of one template";
     return KSG_E_RANGE;
@@ -206,43 +176,38 @@ int scale_up_run(Engine& eng, const ScaleUpIn& in, ScaleUp* out, int32_t* plan, 
   const size_t back_bytes = plan ? (size_t)P * sizeof(int32_t) : (size_t)T * sizeof(ScaleUp);
   if (!back_bytes) return KSG_OK;
   // the launch inputs: the base loads, the pod list, the templates; behind them the open bytes
-  const size_t base_bytes = (size_t)T * sizeof(ScaleBase), pods_bytes = (size_t)P * sizeof(uint32_t);
-  const size_t in_bytes = base_bytes + pods_bytes + (size_t)T * sizeof(uint32_t);
-  const size_t open_bytes = (size_t)T * P;
-  std::vector<uint8_t> host(in_bytes);
-  {
-    ScaleBase* hb = reinterpret_cast<ScaleBase*>(host.data());
-    for (uint32_t i = 0; i < T; ++i) {
-      std::memcpy(hb[i].req, in.base_req + (size_t)i * KSG_MAX_RES, sizeof(hb[i].req));
-      hb[i].pods = in.base_pods[i];
-      hb[i].pad = 0;
-    }
-    if (P) std::memcpy(host.data() + base_bytes, in.pods, pods_bytes);
-    std::memcpy(host.data() + base_bytes + pods_bytes, in.templates, (size_t)T * sizeof(uint32_t));
+  SqIn li;
+  const size_t at_base = li.add<ScaleBase>(T), at_pods = li.add<uint32_t>(P), at_tmpl = li.add<uint32_t>(T);
+  const size_t at_open = li.reserve((size_t)T * P);
+  li.stage();
+  if (P) std::memcpy(li.host<uint32_t>(at_pods), in.pods, (size_t)P * sizeof(uint32_t));
+  std::memcpy(li.host<uint32_t>(at_tmpl), in.templates, (size_t)T * sizeof(uint32_t));
+  for (uint32_t i = 0; i < T; ++i) {
+    ScaleBase& b = li.host<ScaleBase>(at_base)[i];
+    std::memcpy(b.req, in.base_req + (size_t)i * KSG_MAX_RES, sizeof(b.req));
+    b.pods = in.base_pods[i];
+    b.pad = 0;
   }
-  if (!I.bf_in.alloc(in_bytes + open_bytes, err) || !I.hr_dev.alloc(back_bytes, err)) return KSG_E_DEVICE;
-  const ScaleBase* d_base = reinterpret_cast<const ScaleBase*>(I.bf_in.p);
-  const uint32_t* d_pods = reinterpret_cast<const uint32_t*>(I.bf_in.p + base_bytes);
-  const uint32_t* d_tmpl = reinterpret_cast<const uint32_t*>(I.bf_in.p + base_bytes + pods_bytes);
-  uint8_t* d_open = I.bf_in.p + in_bytes;
   uint32_t has_nodename = 0;
   for (int pos = 0; pos < I.F.n; ++pos) has_nodename |= I.F.plugins[pos] == KP_NODENAME;
   auto enqueue = [&](hipStream_t s) -> bool {
-    HIPCHK(hipMemcpyAsync(I.bf_in.p, host.data(), in_bytes, hipMemcpyHostToDevice, s));
+    const ScaleBase* d_base = li.dev<const ScaleBase>(at_base);
+    const uint32_t* d_pods = li.dev<const uint32_t>(at_pods);
+    const uint32_t* d_tmpl = li.dev<const uint32_t>(at_tmpl);
+    uint8_t* d_open = li.dev<uint8_t>(at_open);
     for (uint32_t t0 = 0; P && t0 < T; t0 += 65535u)  // (grid.y <= 65535)
       hipLaunchKernelGGL(k_scale_open, dim3((P + 255) / 256, std::min(T - t0, 65535u)), dim3(256), 0, s, I.cluster(), I.F,
                          I.progs.p, I.prog_off_d.p, d_pods, P, d_tmpl + t0, has_nodename, d_open + (size_t)t0 * P);
     if (plan)
       hipLaunchKernelGGL(k_scale_pack<true>, dim3(1), dim3(256), 0, s, I.cluster(), I.progs.p, I.prog_off_d.p, d_pods, P,
-                         d_tmpl, d_base, d_open, in.max_nodes, (ScaleUp*)nullptr, reinterpret_cast<int32_t*>(I.hr_dev.p));
+                         d_tmpl, d_base, d_open, in.max_nodes, (ScaleUp*)nullptr, reinterpret_cast<int32_t*>(I.sq_out.p));
     else
       hipLaunchKernelGGL(k_scale_pack<false>, dim3(T), dim3(256), 0, s, I.cluster(), I.progs.p, I.prog_off_d.p, d_pods, P,
-                         d_tmpl, d_base, d_open, in.max_nodes, reinterpret_cast<ScaleUp*>(I.hr_dev.p), (int32_t*)nullptr);
+                         d_tmpl, d_base, d_open, in.max_nodes, reinterpret_cast<ScaleUp*>(I.sq_out.p), (int32_t*)nullptr);
     return true;
   };
-  if (!sq_fetch(I, I.hr_dev.p, back_bytes, enqueue, err)) return KSG_E_DEVICE;
-  std::memcpy(plan ? (void*)plan : (void*)out, I.sq_host.p, back_bytes);
-  return KSG_OK;
+  void* dst = plan ? (void*)plan : (void*)out;
+  return sq_fetch(I, &li, back_bytes, 0, back_bytes, dst, enqueue, err) ? KSG_OK : KSG_E_DEVICE;
 }
 }  // namespace
 

@@ -118,6 +118,17 @@ def test_node_tile_edges(n_nodes):
         s.close()
 
 
+def test_first_hit_rotation():
+    """One block, eight subjects of four sizes over three tiles: hits in tile 0, 2, none, 1, 1, 0, 2, none, so
+    the rotation of the three first-hit words passes every residue with a hit and without one.  The plan is
+    test_drain_model's literal, checked there against the model and the oracle."""
+    s = load(m.rotation_doc())
+    assert s.drain_plan(m.ROTATION_X) == m.ROTATION_PLAN
+    got = s.drain(m.ROTATION_X, 1)[0]
+    assert tuple(got) == tuple(m.ROTATION_DRAIN) and not got.drainable
+    s.close()
+
+
 # ------------------------------------------------------------------ 3: the cap
 def test_cap(monkeypatch):
     """KSG_DRAIN_MAX=4 at ksg_create: of six subjects four are simulated, two skipped."""

@@ -250,6 +250,48 @@ def edge_cases(n_nodes):
     return out
 
 
+# The first-hit rotation (k_drain's tile step, csrc/drain.hip; SqFirstHit in csrc/snapshot_query.hip states
+# the argument): a tile step uses one of three LDS words,
+# chosen by a count of the steps since the drain began.  None of edge_cases' drains goes back to a lower tile
+# (its subjects are all alike, so their destinations only ascend); here they differ in size.  Three tiles; the
+# only rooms are 1000m on node 7 (tile 0), 4000m on T + 5 (tile 1), 16000m on the last node (tile 2).
+# A subject of 200m hits in tile 0 (one step), of 1500m in tile 1 (an empty step, a hit), of 5000m in
+# tile 2 (two empty steps, a hit), of 20000m nowhere (three empty steps).
+ROTATION_X = 3
+ROTATION_CPU = [200, 5000, 20000, 1500, 1500, 200, 5000, 20000]
+ROTATION_PLAN = [(0, 7), (1, 2 * TILE + 51), (2, -1), (3, TILE + 5), (4, TILE + 5), (5, 7), (6, 2 * TILE + 51), (7, -1)]
+ROTATION_DRAIN = Drain(8, 0, 6, 2, 0, 2, 3)
+
+
+def rotation_doc():
+    doc = edge_doc(2 * TILE + 52, {7: 1000, TILE + 5: 4000, 2 * TILE + 51: 16000}, {})
+    name = doc["nodes"][ROTATION_X]["metadata"]["name"]
+    doc["pods"] = [g.pod_obj(f"r{j}", [g.req(cpu, g.Gi)], node=name) for j, cpu in enumerate(ROTATION_CPU)]
+    return doc
+
+
+def rotation_steps(plan, n_tiles=3):
+    """[(step count % 3, found)] of the tile steps a plan's subjects take, in order: a subject walks the
+    tiles from 0 up to its destination's, or all of them if it has none."""
+    out = []
+    for _, dest in plan:
+        last = dest // TILE if dest >= 0 else n_tiles - 1
+        for t in range(last + 1):
+            out.append((len(out) % 3, dest >= 0 and t == last))
+    return out
+
+
+def test_first_hit_rotation():
+    """The literal plan equals the model and the oracle; over it the step count passes every residue both
+    with a hit and without, and the subjects' step counts (1, 3, 3, 2, 2, 1, 3, 3) have no period of 3."""
+    doc = rotation_doc()
+    assert simulate(doc, ROTATION_X) == (ROTATION_DRAIN, ROTATION_PLAN)
+    assert oracle_plan(doc, ROTATION_X) == ROTATION_PLAN
+    steps = rotation_steps(ROTATION_PLAN)
+    assert steps[:4] == [(0, True), (1, False), (2, False), (0, True)] and len(steps) == 18
+    assert set(steps) == {(r, f) for r in range(3) for f in (False, True)}
+
+
 @pytest.mark.parametrize("n_nodes", [TILE - 1, TILE, TILE + 1, 2 * TILE + 52])
 def test_tile_shapes(n_nodes):
     """The tile-edge builders: the literal destinations equal the model; one candidate of each against the oracle."""

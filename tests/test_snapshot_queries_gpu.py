@@ -1,12 +1,15 @@
 """The snapshot queries on one context, interleaved (csrc/snapshot_query.hip): headroom, the
-eviction fit, the diagnosis and the ranked candidates share one pinned block and one host gate,
-while their own tests run each on a context of its own.
+eviction fit, the drain and scale-up simulations, the diagnosis and the ranked candidates share one
+pinned block and one host gate, and the first four the device buffers of their launch inputs
+(sq_in) and answers (sq_out), while their own tests run each on a context of its own.
 
-The sequence makes the block grow (one struct, a node row, 33 structs), be used below its capacity
-and grow again, and crosses one tile boundary on each axis: 1,025 nodes (kSqTile = 1024), 33 queue
-pods and 33 bound pods (kSqPods = 32).  Every answer is compared with the same call made as the
-first query of a fresh context of the same cluster, whose answers the features' own tests check
-against their references.
+The sequence makes the pinned block and either device buffer grow, be used below capacity and grow
+again (small, large, small, large; the sizes stand beside the steps), and crosses one tile boundary
+on each axis: 1,025 nodes (kSqTile = 1024), 33 queue pods and 33 bound pods (kSqPods = 32).  The
+scale-up of all 33 pods follows the plan of one node's drain, so its open bytes, which lie behind
+its inputs and are never uploaded, land on a freshly grown sq_in.  Every answer is compared with
+the same call made as the first query of a fresh context of the same cluster, whose answers the
+features' own tests check against their references.
 """
 import copy
 
@@ -47,13 +50,18 @@ def test_interleaved_calls_equal_a_fresh_context():
     q = b = POD_TILE  # the one pod of the second pod tile, on either axis
     s = load(doc)
     assert (s.n_nodes, s.queue_len, s.bound_count) == (TILE + 1, POD_TILE + 1, POD_TILE + 1)
-    steps = [
-        lambda x: x.headroom(0, 1),
-        lambda x: x.bound_fit_nodes(b),
-        lambda x: x.headroom(0, POD_TILE + 1),
-        lambda x: x.node_evictability(),
-        lambda x: x.bound_fit(0, POD_TILE + 1),
-        lambda x: x.headroom_nodes(q),
+    every = list(range(POD_TILE + 1))
+    steps = [                                                # bytes of   sq_in             sq_out
+        lambda x: x.headroom(0, 1),                          #            -                 64
+        lambda x: x.drain_plan(0),                           # (1 pod)    28: first use     8
+        lambda x: x.scale_up(every, [0, TILE], 16),          #            288 + 66: grows   64
+        lambda x: x.bound_fit_nodes(b),                      #            12                4,100: grows
+        lambda x: x.headroom(0, POD_TILE + 1),               #            -                 2,112
+        lambda x: x.drain(0, TILE + 1),                      #            16,796: grows     32,800: grows
+        lambda x: x.scale_up_plan(every, TILE, 16),          #            216 + 33          132
+        lambda x: x.node_evictability(),                     #            396               16,928
+        lambda x: x.bound_fit(0, POD_TILE + 1),              #            396               528
+        lambda x: x.headroom_nodes(q),                       #            -                 4,100
     ]
     for i, call in enumerate(steps):
         want = call(load(doc))
