@@ -55,7 +55,8 @@ extern "C" {
  * ksg_bound_pod, ksg_bound_fit (the call and the struct), ksg_bound_fit_nodes,
  * ksg_node_evictability, ksg_node_evict; ksg_drain (the call and the struct),
  * ksg_drain_plan, ksg_drain_move, KSG_DRAIN_MAX; ksg_scale_up (the call and the
- * struct), ksg_scale_up_plan, KSG_SCALE_MAX. */
+ * struct), ksg_scale_up_plan, KSG_SCALE_MAX; ksg_drain_sets, ksg_drain_prefixes,
+ * ksg_drain_set_plan, ksg_drain_set (the struct), KSG_DRAIN_SET_NODES. */
 #define KSG_ABI_VERSION 4
 
 #define KSG_OK 0
@@ -531,6 +532,74 @@ struct ksg_drain {            /* 32 bytes, per candidate node */
 struct ksg_drain_move { int32_t bound; int32_t dest; };  /* dest: global node, -1 unplaced, -2 skipped */
 int ksg_drain(ksg_ctx* ctx, uint32_t first_node, uint32_t count, struct ksg_drain* out);
 int ksg_drain_plan(ksg_ctx* ctx, uint32_t node, struct ksg_drain_move* out, uint32_t cap, uint32_t* n_out);
+
+/* Set drain (the cluster-autoscaler's cumulative scale-down simulation, Karpenter's
+ * multi-node consolidation): can these nodes be removed together.  ksg_drain
+ * judges every candidate alone: two nodes that are each drainable may send their
+ * pods to the same room, or one to the other.  Here the nodes of a set leave
+ * together, in one simulation.  One block per set on the device
+ * (csrc/drain_set.hip), every set of a call in one launch.
+ * Sets.  Set i is the local nodes nodes[set_start[i] .. set_start[i + 1]), in the
+ * caller's order; set_start has n_sets + 1 entries and does not descend.  The
+ * order matters and the call does not sort: the same nodes in another order may
+ * give another plan and another answer.  A set holds at most
+ * KSG_DRAIN_SET_NODES nodes, each once.
+ * Subjects.  The set's nodes in list order, and within a node its drain subjects
+ * exactly as ksg_drain defines them: ascending bound index, DaemonSet-owned and
+ * mirror pods left out.  Those go with their node and are counted in `daemon`.
+ * Destinations.  For subject b, in order, dest(b) is the lowest global node index
+ * not in the set whose code is KSG_FILTER_PASSED.  The code is that of
+ * ksg_bound_fit_nodes (NodeName's Filter is not applied) with every earlier
+ * placement of this set's simulation counted on its destination (requests and pod
+ * count), from whichever member it came.  A member is never a destination,
+ * neither an earlier one of the list nor a later one.  A subject with no such
+ * node is unplaced; it changes nothing and the simulation goes on with the next.
+ * At most KSG_DRAIN_MAX subjects are simulated per set (the engine's effective
+ * cap: the environment override of ksg_drain holds here too); the rest are counted
+ * in `skipped` and get dest -2 in the plan.  A set is removable when
+ * unplaced == 0 && skipped == 0.  first_blocked is the position in the set's list
+ * of the first node one of whose subjects is unplaced or skipped: the prefix
+ * before it went through.
+ * First fit in node order, as in ksg_drain: deterministic and what a scale-down
+ * simulation does, and not the scheduler's choice.  A real cycle scores the
+ * feasible nodes, so the pods of a real removal may land elsewhere: the answer
+ * says that a placement exists for this order, not which one will be made.  A set
+ * of one node x equals ksg_drain of x, field by field (first_blocked is then 0 or
+ * -1), and its plan equals ksg_drain_plan(x).
+ * ksg_drain_sets fills out[i] for set i.  ksg_drain_prefixes fills out[k] with the
+ * answer for the set nodes[0 .. k] inclusive, for every k < n, in one launch: a
+ * longer prefix excludes more destinations, so it is no continuation of a shorter
+ * one, and every prefix is simulated from the start.  ksg_drain_set_plan returns
+ * one set's subjects in simulation order with their destinations, buffer
+ * convention of ksg_drain_plan: *n_out receives the number of subjects, cap too
+ * small: KSG_E_NOBUF with the needed count.
+ * Profiles, refusals and errors are those of ksg_drain: a NULL context, a profile
+ * outside headroom's closed form or a sharded context: KSG_E_INVALID.  A required
+ * pointer that is NULL with a non-zero count (nodes, set_start, out, n_out), a
+ * descending set_start, a node outside the local nodes, a set (or n) of more than
+ * KSG_DRAIN_SET_NODES nodes: KSG_E_RANGE.  A node listed twice in one set (for
+ * ksg_drain_prefixes and ksg_drain_set_plan: in the list): KSG_E_INVALID, the
+ * message names the node.  n_sets == 0 or n == 0: KSG_OK, nothing written.  An
+ * empty set: all counts 0, first_unplaced and first_blocked -1.  Nothing is moved
+ * and no scheduling state changes; sets are independent of each other; two calls
+ * return the same bytes.  Indices in the answer are host bound indices and global
+ * node indices. */
+#define KSG_DRAIN_SET_NODES 128          /* nodes per set */
+struct ksg_drain_set {        /* 32 bytes, per set */
+  int32_t pods;            /* bound pods on the set's nodes */
+  int32_t daemon;          /* of them DaemonSet-owned or mirror pods: they go with their node */
+  int32_t placed;          /* subjects that found a destination */
+  int32_t unplaced;        /* subjects that found none */
+  int32_t skipped;         /* subjects beyond the cap: not simulated */
+  int32_t first_unplaced;  /* bound index of the first unplaced subject, -1 when none */
+  int32_t first_blocked;   /* position in the set's list of the first node with an unplaced or skipped subject, -1 */
+  int32_t dest_nodes;      /* distinct destination nodes */
+};                          /* removable: unplaced == 0 && skipped == 0 */
+int ksg_drain_sets(ksg_ctx* ctx, const uint32_t* nodes, const uint32_t* set_start, uint32_t n_sets,
+                   struct ksg_drain_set* out);
+int ksg_drain_prefixes(ksg_ctx* ctx, const uint32_t* nodes, uint32_t n, struct ksg_drain_set* out);
+int ksg_drain_set_plan(ksg_ctx* ctx, const uint32_t* nodes, uint32_t n, struct ksg_drain_move* out, uint32_t cap,
+                       uint32_t* n_out);
 
 /* Scale-up simulation (the cluster-autoscaler's scale-up estimate, its binpacking
  * estimator; Karpenter's provisioning loop): for pods that do not fit, which node

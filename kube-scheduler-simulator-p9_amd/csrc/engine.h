@@ -15,6 +15,7 @@ struct ksg_bound_fit;
 struct ksg_node_evict;
 struct ksg_drain;
 struct ksg_drain_move;
+struct ksg_drain_set;
 struct ksg_scale_up;
 struct ksg_ctx;
 
@@ -387,6 +388,37 @@ struct DrainIn {
 using DrainFn = int (*)(Engine& eng, const DrainIn& in, struct ::ksg_drain* out, struct ::ksg_drain_move* plan,
                         std::string& err);
 
+// What the set drain's entry points (drain_set.hip) get from host.cpp's
+// drain_set_call.  members: every set's nodes sorted ascending, each with its
+// position in the caller's list; a node of the range counts as a member when its
+// position is below the set's limit (the set size; for prefix k all sets share one
+// sorted list and the limit is k + 1).  subj / subj_pos: the subjects in
+// simulation order -- the set's nodes in list order, within a node ascending
+// bound index, the pods a drain leaves in place taken out -- with the list
+// position of each subject's node; the ranges of prefixes overlap.  Exactly one
+// of out (a struct per set) and plan (n_sets == 1: a move per subject) is set.
+struct DrainSetMember {
+  uint32_t node, pos;  // local node, position in the set's list
+};
+struct DrainSetDesc {              // 32 bytes; the kernel reads it as it stands
+  uint32_t m_start, m_count;       // members [m_start, m_start + m_count), m_count <= KSG_DRAIN_SET_NODES
+  uint32_t limit;                  // positions below it are in the set
+  uint32_t s_start, s_count;       // subjects [s_start, s_start + s_count)
+  int32_t pods, daemon;            // bound pods on the set's nodes; of them left in place
+  uint32_t reserved;
+};
+struct DrainSetIn {
+  uint32_t n_sets;
+  const DrainSetDesc* sets;        // [n_sets]
+  const DrainSetMember* members;
+  uint32_t n_members;
+  const int32_t* subj;             // [n_subjects] bound indices
+  const uint32_t* subj_pos;        // [n_subjects]
+  uint32_t n_subjects;
+};
+using DrainSetFn = int (*)(Engine& eng, const DrainSetIn& in, struct ::ksg_drain_set* out, struct ::ksg_drain_move* plan,
+                           std::string& err);
+
 // What the scale-up simulation's entry points (scale_up.hip) get from host.cpp's
 // scale_up_call: the pod list (queue indices, checked), the templates (local
 // nodes, checked) and per template the base load a fresh node starts with -- the
@@ -427,6 +459,11 @@ int bound_fit_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool whole, boo
 // ksg_drain (out) / ksg_drain_plan (plan, cap, n_out: first is the node, count 1)
 int drain_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const char* what, DrainFn fn,
                struct ::ksg_drain* out, struct ::ksg_drain_move* plan, uint32_t cap, uint32_t* n_out);
+// ksg_drain_sets (set_start, out) / ksg_drain_prefixes (set_start NULL, out: n_sets is n, set k is nodes[0 .. k]) /
+// ksg_drain_set_plan (set_start NULL, plan, cap, n_out: n_sets is n, the one set is nodes[0 .. n))
+int drain_set_call(ksg_ctx* ctx, const uint32_t* nodes, const uint32_t* set_start, uint32_t n_sets, bool args_ok,
+                   const char* what, DrainSetFn fn, struct ::ksg_drain_set* out, struct ::ksg_drain_move* plan,
+                   uint32_t cap, uint32_t* n_out);
 // ksg_scale_up (out) / ksg_scale_up_plan (plan: one template)
 int scale_up_call(ksg_ctx* ctx, const uint32_t* pods, uint32_t n_pods, const uint32_t* templates, uint32_t n_templates,
                   uint32_t max_nodes, bool args_ok, const char* what, ScaleUpFn fn, struct ::ksg_scale_up* out,

@@ -8750,4 +8750,5 @@ extern "C" int ksg_debug_arith(int op, const int64_t* in, uint32_t cols, int64_t
 #include "headroom.hip"
 #include "bound_fit.hip"
 #include "drain.hip"
+#include "drain_set.hip"
 #include "scale_up.hip"

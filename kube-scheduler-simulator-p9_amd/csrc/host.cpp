@@ -5845,6 +5845,81 @@ int drain_call(ksg_ctx* ctx, uint32_t first, uint32_t count, bool args_ok, const
   return ctx->done(fn(*c.eng, in, out, plan, c.err));
 }
 
+// The set drain: the drain's refusals and its store; the call has no range, its
+// lists are checked under the lock the gate took: the sizes, the nodes, then a
+// node listed twice (the sorted member list shows it).  The subjects are the
+// sets' nodes in list order, each node's as drain_call takes them, with the list
+// position of their node.  Prefixes (set_start NULL, no plan) share one member
+// list and one subject list: prefix k is the members with a position below k + 1
+// and the subjects of nodes[0 .. k].  The plan of one set is sized here, before
+// the device is asked anything.
+int drain_set_call(ksg_ctx* ctx, const uint32_t* nodes, const uint32_t* set_start, uint32_t n_sets, bool args_ok,
+                   const char* what, DrainSetFn fn, struct ::ksg_drain_set* out, struct ::ksg_drain_move* plan,
+                   uint32_t cap, uint32_t* n_out) {
+  std::unique_lock<std::recursive_mutex> lk;
+  if (const int rc = snapshot_gate(ctx, lk, what, kGateClosedForm, args_ok, 0, nullptr)) return rc;
+  auto& c = ctx->c;
+  if (!n_sets) return KSG_OK;
+  const auto range = [&] { return ctx->fail(std::string(what) + ": range", KSG_E_RANGE); };
+  // the lists: [lo, hi) of nodes per list, one per set, or the one list of prefixes and plan
+  const uint32_t n_lists = set_start ? n_sets : 1;
+  const uint32_t first = set_start ? set_start[0] : 0, end = set_start ? set_start[n_sets] : n_sets;
+  for (uint32_t i = 0; i < n_lists; ++i) {
+    const uint32_t lo = set_start ? set_start[i] : 0, hi = set_start ? set_start[i + 1] : n_sets;
+    if (hi < lo || hi - lo > KSG_DRAIN_SET_NODES) return range();
+  }
+  if (end > first && !nodes) return range();
+  for (uint32_t i = first; i < end; ++i)
+    if (nodes[i] >= c.hi - c.lo) return range();
+  std::vector<DrainSetMember> members(end - first);
+  for (uint32_t i = 0; i < n_lists; ++i) {
+    const uint32_t lo = set_start ? set_start[i] : 0, hi = set_start ? set_start[i + 1] : n_sets;
+    DrainSetMember* m = members.data() + (lo - first);
+    for (uint32_t j = lo; j < hi; ++j) m[j - lo] = DrainSetMember{nodes[j], j - lo};
+    std::sort(m, m + (hi - lo), [](const DrainSetMember& a, const DrainSetMember& b) { return a.node < b.node; });
+    for (uint32_t j = 1; j < hi - lo; ++j)
+      if (m[j].node == m[j - 1].node) {
+        const size_t g = (size_t)c.lo + m[j].node;
+        return ctx->fail(std::string(what) + ": node " + std::to_string(m[j].node) +
+                             (g < c.node_names.names.size() ? " (" + c.node_names.names[g] + ")" : std::string()) +
+                             " is listed twice" + (set_start ? " in set " + std::to_string(i) : std::string()),
+                         KSG_E_INVALID);
+      }
+  }
+  // the subjects, list by list; at[j]: the subjects, the bound pods and those left in place before list entry j
+  const std::vector<uint32_t>& boff = c.bound_by_node();
+  std::vector<int32_t> subj;
+  std::vector<uint32_t> subj_pos;
+  std::vector<DrainSetDesc> sets(plan ? 1 : n_sets);
+  for (uint32_t i = 0; i < n_lists; ++i) {
+    const uint32_t lo = set_start ? set_start[i] : 0, hi = set_start ? set_start[i + 1] : n_sets;
+    const uint32_t s_start = (uint32_t)subj.size();
+    int32_t pods = 0, daemon = 0;
+    for (uint32_t j = lo; j < hi; ++j) {
+      pods += (int32_t)bound_on_node(c, boff, nodes[j], [&](int32_t b, bool stays) {
+        if (stays) {
+          ++daemon;
+        } else {
+          subj.push_back(b);
+          subj_pos.push_back(j - lo);
+        }
+      });
+      if (!set_start && !plan)  // prefix j
+        sets[j] = DrainSetDesc{0, hi, j + 1, s_start, (uint32_t)subj.size() - s_start, pods, daemon, 0};
+    }
+    if (set_start || plan)
+      sets[i] = DrainSetDesc{lo - first, hi - lo, hi - lo, s_start, (uint32_t)subj.size() - s_start, pods, daemon, 0};
+  }
+  if (plan) {
+    *n_out = (uint32_t)subj.size();
+    if (cap < subj.size()) return KSG_E_NOBUF;
+  }
+  if (const int rc = programs_ready(ctx, true)) return rc;
+  const DrainSetIn in{plan ? 1u : n_sets, sets.data(),    members.data(),      (uint32_t)members.size(),
+                      subj.data(),        subj_pos.data(), (uint32_t)subj.size()};
+  return ctx->done(fn(*c.eng, in, out, plan, c.err));
+}
+
 // The scale-up simulation: the drain's refusals; the call has no range, its lists
 // are checked under the lock the gate took.  The listed queue pods' programs are
 // compiled and refreshed as headroom's; the base load of a template is summed

@@ -87,6 +87,24 @@ class Drain(namedtuple("Drain", "pods daemon placed unplaced skipped first_unpla
         return self.unplaced == 0 and self.skipped == 0
 
 
+DRAIN_SET_NODES = 128  # KSG_DRAIN_SET_NODES
+
+
+class _DrainSet(ctypes.Structure):
+    _fields_ = [("pods", ctypes.c_int32), ("daemon", ctypes.c_int32), ("placed", ctypes.c_int32),
+                ("unplaced", ctypes.c_int32), ("skipped", ctypes.c_int32), ("first_unplaced", ctypes.c_int32),
+                ("first_blocked", ctypes.c_int32), ("dest_nodes", ctypes.c_int32)]
+
+
+class DrainSet(namedtuple("DrainSet", "pods daemon placed unplaced skipped first_unplaced first_blocked dest_nodes")):
+    __slots__ = ()
+
+    @property
+    def removable(self):
+        """Every subject of the set was simulated and found a destination outside it."""
+        return self.unplaced == 0 and self.skipped == 0
+
+
 SCALE_MAX = 1024  # KSG_SCALE_MAX
 
 
@@ -739,8 +757,60 @@ class Scheduler:
         self._chk(rc, "ksg_drain_plan")
         return [(a.bound, a.dest) for a in arr[:n.value]]
 
-    # ---- scale-up simulation (ksg.h): a pod list packed onto fresh nodes of a template, first fit in bin order
+    # ---- set drain (ksg.h): several nodes removed together, one simulation per set, first fit in node order
     _U32P = ctypes.POINTER(ctypes.c_uint32)
+
+    @staticmethod
+    def _drain_sets_out(arr, n):
+        return [DrainSet(a.pods, a.daemon, a.placed, a.unplaced, a.skipped, a.first_unplaced, a.first_blocked,
+                         a.dest_nodes) for a in arr[:n]]
+
+    def drain_sets(self, sets):
+        """ksg_drain_sets: per list of local nodes in `sets` the simulated removal of these nodes together:
+        [DrainSet(pods, daemon, placed, unplaced, skipped, first_unplaced, first_blocked, dest_nodes)],
+        .removable when every subject found a node outside the set.  The subjects are taken in list order
+        (the call does not sort) and no member is a destination.  One launch for all sets."""
+        self.L.ksg_drain_sets.argtypes = [ctypes.c_void_p, self._U32P, self._U32P, ctypes.c_uint32,
+                                          ctypes.POINTER(_DrainSet)]
+        sets = [list(x) for x in sets]
+        flat = [n for x in sets for n in x]
+        start = [0]
+        for x in sets:
+            start.append(start[-1] + len(x))
+        nodes = (ctypes.c_uint32 * max(len(flat), 1))(*flat)
+        st = (ctypes.c_uint32 * len(start))(*start)
+        arr = (_DrainSet * max(len(sets), 1))()
+        self._chk(self.L.ksg_drain_sets(self.h, nodes, st, len(sets), arr), "ksg_drain_sets")
+        return self._drain_sets_out(arr, len(sets))
+
+    def drain_prefixes(self, nodes):
+        """ksg_drain_prefixes: entry k is drain_sets([nodes[:k + 1]])[0], for every k, in one launch."""
+        self.L.ksg_drain_prefixes.argtypes = [ctypes.c_void_p, self._U32P, ctypes.c_uint32, ctypes.POINTER(_DrainSet)]
+        nodes = list(nodes)
+        p = (ctypes.c_uint32 * max(len(nodes), 1))(*nodes)
+        arr = (_DrainSet * max(len(nodes), 1))()
+        self._chk(self.L.ksg_drain_prefixes(self.h, p, len(nodes), arr), "ksg_drain_prefixes")
+        return self._drain_sets_out(arr, len(nodes))
+
+    def drain_set_plan(self, nodes):
+        """ksg_drain_set_plan: the subjects of the set `nodes` in simulation order, [(bound index,
+        destination)]: a global node index, -1 unplaced, -2 beyond KSG_DRAIN_MAX (not simulated)."""
+        self.L.ksg_drain_set_plan.argtypes = [ctypes.c_void_p, self._U32P, ctypes.c_uint32, ctypes.POINTER(_DrainMove),
+                                              ctypes.c_uint32, self._U32P]
+        nodes = list(nodes)
+        p = (ctypes.c_uint32 * max(len(nodes), 1))(*nodes)
+        n = ctypes.c_uint32()
+        cap = 128  # (KSG_E_NOBUF leaves the count in n)
+        while True:
+            arr = (_DrainMove * cap)()
+            rc = self.L.ksg_drain_set_plan(self.h, p, len(nodes), arr, cap, ctypes.byref(n))
+            if rc != -5:
+                break
+            cap = n.value
+        self._chk(rc, "ksg_drain_set_plan")
+        return [(a.bound, a.dest) for a in arr[:n.value]]
+
+    # ---- scale-up simulation (ksg.h): a pod list packed onto fresh nodes of a template, first fit in bin order
 
     def scale_up(self, pods, templates, max_nodes=SCALE_MAX):
         """ksg_scale_up: the queue indices `pods`, in this order, packed onto fresh nodes shaped like each
