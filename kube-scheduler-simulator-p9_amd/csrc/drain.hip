@@ -179,52 +179,72 @@ __global__ __launch_bounds__(256) void k_drain(DevCluster C, DevProfile F, const
 }
 
 namespace {
+// A drain call's subjects as launch inputs (drain_run, and drain_set_run in drain_set.hip), behind the
+// arrays the caller has laid out in `li`: their victim-store offsets (at_off) and bound indices (at_bidx)
+// are laid out, `li` is staged and both are filled.  false: err is set (KSG_E_STATE).
+bool drain_subjects(const Engine::Impl& I, SqIn& li, const int32_t* subj, uint32_t total, const char* what,
+                    size_t& at_off, size_t& at_bidx, std::string& err) {
+  at_off = li.add<uint64_t>(total);
+  at_bidx = li.add<int32_t>(total);
+  li.stage();
+  uint64_t* h_off = li.host<uint64_t>(at_off);
+  if (total) std::memcpy(li.host<int32_t>(at_bidx), subj, (size_t)total * sizeof(int32_t));
+  for (uint32_t i = 0; i < total; ++i) {
+    const int32_t b = subj[i];
+    if (b < 0 || (size_t)b >= I.vstore_off.size()) {  // (host.cpp ensured the store for this very bound list)
+      err = std::string(what) + ": bound pod outside the victim store";
+      return false;
+    }
+    h_off[i] = I.vstore_off[(size_t)b];
+  }
+  return true;
+}
+
+// A drain call's launch and round trip.  launch(is_plan, grid, stream) enqueues the kernel's <true>
+// instantiation on one block for a plan (is_plan: std::true_type), its <false> instantiation on `blocks`
+// otherwise; either writes I.sq_out, and back_bytes of it come back through the pinned block into plan
+// or out, one synchronisation.
+template <class T>
+T* drain_out(Engine::Impl& I, bool used) {  // (null for the pointer an instantiation does not touch)
+  return used ? reinterpret_cast<T*>(I.sq_out.p) : nullptr;
+}
+template <class Launch>
+int drain_fetch(Engine::Impl& I, SqIn& li, size_t back_bytes, uint32_t blocks, void* out, DrainMove* plan,
+                std::string& err, Launch launch) {
+  auto enqueue = [&](hipStream_t s) -> bool {
+    if (plan) launch(std::true_type{}, dim3(1), s);
+    else launch(std::false_type{}, dim3(blocks), s);
+    return true;
+  };
+  return sq_fetch(I, &li, back_bytes, 0, back_bytes, plan ? (void*)plan : out, enqueue, err) ? KSG_OK : KSG_E_DEVICE;
+}
+
 // The candidates of `in` against the snapshot as the stream holds it: the launch
 // inputs through the device buffer, the structs (or the one candidate's moves)
 // back through the pinned block, one synchronisation.
 int drain_run(Engine& eng, const DrainIn& in, Drain* out, DrainMove* plan, std::string& err) {
   Engine::Impl& I = *eng.impl();
-  const uint32_t N = I.N;
   if (!sq_need_fit(I, "drain", err)) return KSG_E_INVALID;
   const uint32_t total = in.start[in.count];
-  if ((size_t)in.first_node + in.count > N || (plan && in.count != 1)) {
+  if ((size_t)in.first_node + in.count > I.N || (plan && in.count != 1)) {
     err = "drain: candidates outside the snapshot";
     return KSG_E_RANGE;
   }
   const size_t back_bytes = plan ? (size_t)total * sizeof(DrainMove) : (size_t)in.count * sizeof(Drain);
   if (!back_bytes) return KSG_OK;
-  // the launch inputs: the subjects' store offsets, the candidates, the subjects' bound indices
+  // the launch inputs: the candidates, then the subjects
   SqIn li;
-  const size_t at_off = li.add<uint64_t>(total), at_cand = li.add<DrainCand>(in.count), at_bidx = li.add<int32_t>(total);
-  li.stage();
-  uint64_t* h_off = li.host<uint64_t>(at_off);
+  size_t at_cand = li.add<DrainCand>(in.count), at_off, at_bidx;
+  if (!drain_subjects(I, li, in.subj, total, "drain", at_off, at_bidx, err)) return KSG_E_STATE;
   DrainCand* h_cand = li.host<DrainCand>(at_cand);
-  if (total) std::memcpy(li.host<int32_t>(at_bidx), in.subj, (size_t)total * sizeof(int32_t));
-  for (uint32_t i = 0; i < total; ++i) {
-    const int32_t b = in.subj[i];
-    if (b < 0 || (size_t)b >= I.vstore_off.size()) {  // (host.cpp ensured the store for this very bound list)
-      err = "drain: bound pod outside the victim store";
-      return KSG_E_STATE;
-    }
-    h_off[i] = I.vstore_off[(size_t)b];
-  }
   for (uint32_t c = 0; c < in.count; ++c)
     h_cand[c] = DrainCand{in.start[c], in.start[c + 1] - in.start[c], in.pods[c], in.daemon[c]};
-  const uint32_t cap = std::min(I.drain_max, kDrainMax), tiles = (N + kSqTile - 1) / kSqTile;
-  auto enqueue = [&](hipStream_t s) -> bool {
-    const DrainCand* d_cand = li.dev<const DrainCand>(at_cand);
-    const uint64_t* d_off = li.dev<const uint64_t>(at_off);
-    const int32_t* d_bidx = li.dev<const int32_t>(at_bidx);
-    if (plan)
-      hipLaunchKernelGGL(k_drain<true>, dim3(1), dim3(256), 0, s, I.cluster(), I.F, I.vstore.p, d_cand, d_off, d_bidx,
-                         in.first_node, cap, tiles, (Drain*)nullptr, reinterpret_cast<DrainMove*>(I.sq_out.p));
-    else
-      hipLaunchKernelGGL(k_drain<false>, dim3(in.count), dim3(256), 0, s, I.cluster(), I.F, I.vstore.p, d_cand, d_off,
-                         d_bidx, in.first_node, cap, tiles, reinterpret_cast<Drain*>(I.sq_out.p), (DrainMove*)nullptr);
-    return true;
-  };
-  void* dst = plan ? (void*)plan : (void*)out;
-  return sq_fetch(I, &li, back_bytes, 0, back_bytes, dst, enqueue, err) ? KSG_OK : KSG_E_DEVICE;
+  const uint32_t cap = std::min(I.drain_max, kDrainMax), tiles = (I.N + kSqTile - 1) / kSqTile;
+  return drain_fetch(I, li, back_bytes, in.count, out, plan, err, [&](auto is_plan, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL(k_drain<decltype(is_plan)::value>, grid, dim3(256), 0, s, I.cluster(), I.F, I.vstore.p,
+                       li.dev<const DrainCand>(at_cand), li.dev<const uint64_t>(at_off), li.dev<const int32_t>(at_bidx),
+                       in.first_node, cap, tiles, drain_out<Drain>(I, !is_plan), drain_out<DrainMove>(I, is_plan));
+  });
 }
 }  // namespace
 

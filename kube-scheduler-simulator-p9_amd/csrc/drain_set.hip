@@ -240,44 +240,21 @@ int drain_set_run(Engine& eng, const DrainSetIn& in, DrainSet* out, DrainMove* p
   const uint32_t total = in.n_subjects;
   const size_t back_bytes = plan ? (size_t)in.sets[0].s_count * sizeof(DrainMove) : (size_t)in.n_sets * sizeof(DrainSet);
   if (!back_bytes) return KSG_OK;
-  // the launch inputs: the subjects' store offsets, the sets, the members, the subjects' bound indices and positions
+  // the launch inputs: the sets, the members and the subjects' positions, then the subjects (drain.hip)
   SqIn li;
-  const size_t at_off = li.add<uint64_t>(total), at_sets = li.add<DrainSetDesc>(in.n_sets),
-               at_mem = li.add<DrainSetMember>(in.n_members), at_bidx = li.add<int32_t>(total),
-               at_pos = li.add<uint32_t>(total);
-  li.stage();
-  uint64_t* h_off = li.host<uint64_t>(at_off);
+  size_t at_sets = li.add<DrainSetDesc>(in.n_sets), at_mem = li.add<DrainSetMember>(in.n_members),
+         at_pos = li.add<uint32_t>(total), at_off, at_bidx;
+  if (!drain_subjects(I, li, in.subj, total, "drain_sets", at_off, at_bidx, err)) return KSG_E_STATE;
   std::memcpy(li.host<DrainSetDesc>(at_sets), in.sets, (size_t)in.n_sets * sizeof(DrainSetDesc));
   if (in.n_members) std::memcpy(li.host<DrainSetMember>(at_mem), in.members, (size_t)in.n_members * sizeof(DrainSetMember));
-  if (total) {
-    std::memcpy(li.host<int32_t>(at_bidx), in.subj, (size_t)total * sizeof(int32_t));
-    std::memcpy(li.host<uint32_t>(at_pos), in.subj_pos, (size_t)total * sizeof(uint32_t));
-  }
-  for (uint32_t i = 0; i < total; ++i) {
-    const int32_t b = in.subj[i];
-    if (b < 0 || (size_t)b >= I.vstore_off.size()) {  // (host.cpp ensured the store for this very bound list)
-      err = "drain_sets: bound pod outside the victim store";
-      return KSG_E_STATE;
-    }
-    h_off[i] = I.vstore_off[(size_t)b];
-  }
+  if (total) std::memcpy(li.host<uint32_t>(at_pos), in.subj_pos, (size_t)total * sizeof(uint32_t));
   const uint32_t cap = std::min(I.drain_max, kDrainMax), tiles = (N + kSqTile - 1) / kSqTile;
-  auto enqueue = [&](hipStream_t s) -> bool {
-    const DrainSetDesc* d_sets = li.dev<const DrainSetDesc>(at_sets);
-    const DrainSetMember* d_mem = li.dev<const DrainSetMember>(at_mem);
-    const uint64_t* d_off = li.dev<const uint64_t>(at_off);
-    const int32_t* d_bidx = li.dev<const int32_t>(at_bidx);
-    const uint32_t* d_pos = li.dev<const uint32_t>(at_pos);
-    if (plan)
-      hipLaunchKernelGGL(k_drain_set<true>, dim3(1), dim3(256), 0, s, I.cluster(), I.F, I.vstore.p, d_sets, d_mem, d_off,
-                         d_bidx, d_pos, cap, tiles, (DrainSet*)nullptr, reinterpret_cast<DrainMove*>(I.sq_out.p));
-    else
-      hipLaunchKernelGGL(k_drain_set<false>, dim3(in.n_sets), dim3(256), 0, s, I.cluster(), I.F, I.vstore.p, d_sets, d_mem,
-                         d_off, d_bidx, d_pos, cap, tiles, reinterpret_cast<DrainSet*>(I.sq_out.p), (DrainMove*)nullptr);
-    return true;
-  };
-  void* dst = plan ? (void*)plan : (void*)out;
-  return sq_fetch(I, &li, back_bytes, 0, back_bytes, dst, enqueue, err) ? KSG_OK : KSG_E_DEVICE;
+  return drain_fetch(I, li, back_bytes, in.n_sets, out, plan, err, [&](auto is_plan, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL(k_drain_set<decltype(is_plan)::value>, grid, dim3(256), 0, s, I.cluster(), I.F, I.vstore.p,
+                       li.dev<const DrainSetDesc>(at_sets), li.dev<const DrainSetMember>(at_mem),
+                       li.dev<const uint64_t>(at_off), li.dev<const int32_t>(at_bidx), li.dev<const uint32_t>(at_pos), cap,
+                       tiles, drain_out<DrainSet>(I, !is_plan), drain_out<DrainMove>(I, is_plan));
+  });
 }
 }  // namespace
 

@@ -143,6 +143,24 @@ def test_node_tile_edges(n_nodes):
         s.close()
 
 
+def test_first_hit_rotation():
+    """test_drain_gpu's rotation case as the one-member set: one k_drain_set block, eight subjects over three
+    tiles with hits in tile 0, 2, none, 1, 1, 0, 2, none, so the three first-hit words pass every residue of
+    the step count with a hit and without one.  The literals are test_drain_model's, checked there against
+    the model and the oracle; first_blocked stands where ksg_drain has `reserved`: the one member, position 0."""
+    s = load(dm.rotation_doc())
+    assert s.n_nodes == 2 * T + 52
+    assert s.drain_set_plan([dm.ROTATION_X]) == dm.ROTATION_PLAN
+    got = s.drain_sets([[dm.ROTATION_X]])
+    assert len(got) == 1
+    d, want = got[0], dm.ROTATION_DRAIN
+    assert (d.pods, d.daemon, d.placed, d.unplaced, d.skipped) == (want.pods, want.daemon, want.placed, want.unplaced,
+                                                                   want.skipped)
+    assert d.first_unplaced == want.first_unplaced and d.dest_nodes == want.dest_nodes
+    assert d.first_blocked == 0 and not d.removable
+    s.close()
+
+
 # ------------------------------------------------------------------ 5: the hash overlay
 @pytest.mark.parametrize("case", sorted(m.HASH_CASES))
 def test_hash_overlay(case, monkeypatch):
