@@ -3951,6 +3951,10 @@ __device__ __forceinline__ const ShallowRows* shallow_rows(const uint8_t* rec) {
 }
 static_assert(KSG_BATCH * sizeof(ShallowRows) <= kRecKeys * sizeof(RowV), "shallow rows fit the rows area");
 static_assert(sizeof(ShallowRows) % 8 == 0, "8-byte words");
+// eval blocks' LDS after the keys and the 192 words of counters / pod record
+// (persistent loop): P_{E-2}'s after rows
+constexpr size_t kEvalRowArea = KSG_BATCH * sizeof(RowV);
+static_assert(kEvalRowArea % 16 == 0, "the stash behind it holds 16-byte entries");
 // The merge of pod b's T tile lists into its candidate record (by the pod's
 // last-arriving tile block): LDS L as win_eval's, pnl / np P_{E-2}'s nodes.
 template <bool PER>
@@ -4024,7 +4028,8 @@ __device__ __forceinline__ void win_eval(const DevCluster& C, const DevProfile& 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   uint32_t* wcount = reinterpret_cast<uint32_t*>(L + 16 * 64);
   const uint32_t b = blk / A.T, tile = blk - b * A.T, q = A.e0 + b;
-  // LDS: keys [16][64] u64 | wcount u32[64] | P_{W-1} nodes i32[32] | pod record, normaliser | wave 0's outputs
+  // LDS: keys [16][64] u64 | wcount u32[64] | P_{E-2} nodes i32[32] | pod record, normaliser |
+  // kEvalRowArea (persistent loop: P_{E-2}'s after rows) | held-back outputs
   // (the pod's fields come from LDS: as vector loads behind the output stores
   // every one of them waited for all outstanding stores)
   PodLite* h = reinterpret_cast<PodLite*>(wcount + 96);
@@ -4041,12 +4046,33 @@ __device__ __forceinline__ void win_eval(const DevCluster& C, const DevProfile& 
     if (tid < kPodW) reinterpret_cast<uint64_t*>(h)[tid] = reinterpret_cast<const uint64_t*>(A.plite + q)[tid];
     if (STAT && tid < 2) mlds[tid] = ldv<PER>(A.mpred + 2 * (q - A.first) + tid);
   }
-  const int np = ldv<PER>(A.pprev_n);
   // P_{W-1}'s nodes in LDS (a lookup through LDS: a VGPR loaded from memory and
   // read lane by lane in a loop made the compiler wait for every outstanding
   // load and store, vmcnt(0), at each lookup)
   int32_t* pnl = reinterpret_cast<int32_t*>(wcount + 64);
-  if (tid < np) pnl[tid] = ldv<PER>(&A.pprev[tid].node);
+  uint64_t* const rarea = reinterpret_cast<uint64_t*>(wcount + 192);
+  int np;
+  if constexpr (PER) {
+    // Persistent loop: the whole of P_{E-2}, nodes and after rows, in the round
+    // trip of the first row load: unused entries hold node -1 (win_fixup's P_W
+    // store; the host before the launch), so no count is read first and a hit
+    // takes its row from LDS.  One word per thread: entry e's node word and the
+    // words of its after row.
+    constexpr int kRowW = (int)(sizeof(RowV) / 8), kPendW = (int)(sizeof(Pend) / 8);
+    static_assert(offsetof(Pend, node) == 0 && offsetof(Pend, after) == (size_t)(kPendW - kRowW) * 8, "Pend words");
+    static_assert(KSG_BATCH * (kRowW + 1) <= KSG_WIN_THREADS, "one word of P_{E-2} per thread");
+    np = KSG_BATCH;
+    if (tid < KSG_BATCH * (kRowW + 1)) {
+      const int e = tid / (kRowW + 1), k = tid - e * (kRowW + 1);
+      const uint64_t* pe = reinterpret_cast<const uint64_t*>(A.pprev + e);
+      const uint64_t v = ld_sc1(pe + (k == 0 ? 0 : kPendW - kRowW + k - 1));
+      if (k == 0) pnl[e] = (int32_t)(uint32_t)v;
+      else rarea[e * kRowW + k - 1] = v;
+    }
+  } else {
+    np = ldv<PER>(A.pprev_n);
+    if (tid < np) pnl[tid] = ldv<PER>(&A.pprev[tid].node);
+  }
   lds_barrier();
   auto pend_lds = [&](int32_t gid) {
     int hit = -1;
@@ -4071,16 +4097,21 @@ __device__ __forceinline__ void win_eval(const DevCluster& C, const DevProfile& 
   // over: wave 0's arrival waits (vmcnt) for all of its stores, and every
   // wave's next-node loads would wait behind its previous node's stores.
   // Tiles of more than KSG_STASH_NPT nodes per thread: only wave 0 stashes.
-  PatchV* stash = reinterpret_cast<PatchV*>(wcount + 192);
+  PatchV* stash = reinterpret_cast<PatchV*>(wcount + 192 + kEvalRowArea / 4);
   const bool stash_all = A.npt <= A.stash_npt;
   static_assert(96 * 4 + sizeof(PodLite) + 16 <= 192 * 4, "eval LDS layout");
+  static_assert((16 * 64 * 8 + 192 * 4) % 16 == 0, "row area and stash alignment");
   // the next node's row and static record are loaded while this one is evaluated
   auto fetch = [&](uint32_t kk, RowV& r, StaticRec& sr, bool loaded) {
     const uint32_t to = kk * KSG_TILE + tid, nn = tile * A.tile_len + to;
     if (to < A.tile_len && nn < C.N) {
       const int hit = pend_lds((int32_t)(C.goff + nn));
-      if (hit >= 0) r = ld_obj<PER>(&A.pprev[hit].after);
-      else if (!loaded) load_row_p<PER>(C, nn, A.need_eph, r);
+      if constexpr (PER) {
+        if (hit >= 0) r = *reinterpret_cast<const RowV*>(rarea + hit * (int)(sizeof(RowV) / 8));
+      } else {
+        if (hit >= 0) r = ld_obj<PER>(&A.pprev[hit].after);
+      }
+      if (hit < 0 && !loaded) load_row_p<PER>(C, nn, A.need_eph, r);
       if (STAT) sr = srec_at<PER>(A, q, C.goff + nn);
     }
   };
@@ -4297,9 +4328,10 @@ struct WinLDS {
 };
 
 static_assert(sizeof(WinLDS) <= 160 * 1024, "window LDS exceeds the CU's 160 KiB");
-// eval blocks: keys [16][64] u64 + 192 u32 of counters / pod record, then the stash
-static constexpr uint32_t kStashNpt =
-    (uint32_t)std::min<size_t>(KSG_STASH_NPT, (sizeof(WinLDS) - (16 * 64 * 8 + 192 * 4)) / (16 * 64 * sizeof(PatchV)));
+// eval blocks: keys [16][64] u64 + 192 u32 of counters / pod record + the row area
+// (kEvalRowArea: P_{E-2}'s after rows), then the stash
+static constexpr uint32_t kStashNpt = (uint32_t)std::min<size_t>(
+    KSG_STASH_NPT, (sizeof(WinLDS) - (16 * 64 * 8 + 192 * 4 + kEvalRowArea)) / (16 * 64 * sizeof(PatchV)));
 static_assert(kStashNpt >= 1, "eval blocks' output stash exceeds the window LDS");
 __device__ __forceinline__ uint32_t hslot(int32_t node) { return ((uint32_t)node * 2654435761u) >> 25; }
 __device__ __forceinline__ int prior_of(const WinLDS& L, int32_t x) {
@@ -4842,7 +4874,9 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
       for (int base = stable * (stable - 1) / 2 + wave * 64; base < p_hi; base += 8 * 64) {
         const int p = base + lane;
         if (p < p_hi) {
-          int b = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
+          // (the hardware square root, 1 ulp, not sqrtf's correctly rounded sequence:
+          // p < 496, so the estimate is within one of b and the next line makes it exact)
+          int b = (int)((1.0f + __builtin_amdgcn_sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
           b = b * (b - 1) / 2 > p ? b - 1 : ((b + 1) * b / 2 <= p ? b + 1 : b);
           const int a = p - b * (b - 1) / 2;
           PickRow& e = L.pr[a];  // (of S[cur]: the guess's, or win_fill_rows')
@@ -5117,7 +5151,30 @@ __device__ __forceinline__ void win_fixup(const DevCluster& C, const DevProfile&
   // ---- flush: P_W first (the persistent loop publishes it at once: the eval
   // blocks of window W+2 wait for it), then summaries and per-pair patches
   const PickTab& T = L.pick[cur];
-  if (wave == 0) {  // P_W: each node picked in the window, by its last pick
+  if constexpr (PER) {
+    // P_W: each node picked in the window, by its last pick, copied from the row
+    // table (base is the origin's start row, after the row under every pick of the
+    // node).  One 64-bit word per thread — thread (a, k) stores word k of entry a's
+    // Pend, consecutive threads consecutive words — not an entry of 23 words per lane
+    // of wave 0: the list leaves in a few full-line stores of twelve waves.  Every
+    // wave takes the same ballot over the table's 32 entries.
+    static_assert(offsetof(PickRow, base) == 0 && offsetof(PickRow, after) == sizeof(RowV), "PickRow: base, after first");
+    static_assert(offsetof(Pend, base) == 8 && offsetof(Pend, after) == 8 + sizeof(RowV), "Pend: node word, base, after");
+    static_assert(KSG_BATCH * kPendW <= KSG_WIN_THREADS, "one word of P_W per thread");
+    const PickRow& e = L.pr[lane & 31];
+    const uint32_t m = (uint32_t)__ballot(lane < nb && e.node >= 0 && e.nx == KSG_BATCH);  // (nb <= 32: lanes 0..31)
+    const int n = __popc(m);
+    const int a = tid / kPendW, k = tid - a * kPendW;
+    if (a < KSG_BATCH && ((m >> a) & 1u)) {
+      const PickRow& src = L.pr[a];
+      const uint64_t v = k == 0 ? (uint64_t)(uint32_t)src.node : reinterpret_cast<const uint64_t*>(&src)[k - 1];
+      st_sc1(reinterpret_cast<uint64_t*>(A.pnext + __popc(m & ((1u << a) - 1u))) + k, v);
+    }
+    // (the unused entries hold node -1, so that the eval blocks read the list
+    // without its count; covered by the vmcnt(0) before the publish)
+    if (tid < KSG_BATCH && tid >= n) st_sc1(reinterpret_cast<uint64_t*>(A.pnext + tid), 0xFFFFFFFFull);
+    if (tid == 0) st_sc1(A.pnext_n, (int32_t)n);
+  } else if (wave == 0) {  // P_W: each node picked in the window, by its last pick
     // (copied from the row table: base is the origin's start row, after the row
     // under every pick of the node)
     const int a = lane;
@@ -5271,6 +5328,9 @@ __global__ void k_rows_unpack(const RowV* recv, uint32_t ranks, uint32_t G, uint
 // boundaries of k_window become hand-offs (agent-scope counters, sc1 data):
 //   eval(E)   starts once replay(E-2) is published (Z.replayed >= E-1): the rows as of
 //             the end of window E-2 (P_{E-2} from its list) — as k_window's eval part;
+//             the list is read whole, without its count: replay(E-2) wrote node -1
+//             into the entries it did not use before that publish (windows 0 and 1:
+//             the host, before the launch);
 //   replay(W) starts once every pod of window W has its candidate record (Z.evd:
 //             the merge's keys, shallow rows and counts; the replay evaluates the
 //             pods on P_{W-1} itself, as k_window's does), and writes its output
@@ -6627,6 +6687,9 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
     HIPCHK(hipMemsetAsync(I.wsync.p, 0, sizeof(WinSync), s));
     HIPCHK(hipMemsetAsync(I.rsync.p, 0, kRunSyncReset, s));
     HIPCHK(hipMemsetAsync(I.arrive.p, 0, 2 * KSG_BATCH * 32 * sizeof(uint32_t), s));
+    // (every entry of both P lists starts unused: node -1, which the eval blocks
+    // read in place of a count; the per-window loop, on a fallback, goes by pend_n)
+    HIPCHK(hipMemsetAsync(I.pend.p, 0xFF, 2 * KSG_BATCH * sizeof(Pend), s));
     WinRunArgs R{};
     R.nwin = nwin;
     R.first = first;

@@ -83,6 +83,9 @@ if any(x[0] for x in lt):
 rp = [buf[nw * 36 + j * 4:nw * 36 + (j + 1) * 4] for j in range(nw)]
 if any(x[2] for x in rp):
     print("realtime (us): publish -> publish", med([(rp[j][2] - rp[j - 1][2]) / 100 for j in range(2, nw)]))
+    # cycle A's hand-over: the evaluation of E starts on the publish of E-2
+    print("realtime (us): publish of E-2 -> eval E start", med([(ev[j] - rp[j - 2][2]) / 100 for j in range(3, nw)]))
+    print("realtime (us): last merge of W -> publish of W", med([(rp[j][2] - bs[j][10]) / 100 for j in range(2, nw)]))
     print("realtime (us): publish of W -> fixup W end (summaries, patches)", med([(bs[j][12] - rp[j][2]) / 100 for j in range(1, nw)]))
 if any(x[1] for x in rp):  # two replay blocks (KSG_WIN_REPLAY2=1): the stage above includes the publish wait
     w = [(rp[j][1] - rp[j][0]) / 100 for j in range(2, nw)]
