@@ -5608,7 +5608,7 @@ struct Engine::Impl {
   Engine::ExchangeFn xfn = nullptr;
   void* xuser = nullptr;
   DBuf<uint8_t> xsend, xrecv;
-  DBuf<RowV> xrows;  // sharded windows: every node's row (run_batches)
+  DBuf<RowV> xrows;  // sharded windows: every node's row (window_setup)
   uint32_t G = 0;    // nodes of the whole cluster
   // host exchange (mode 2): pinned staging buffers; the callback runs as a
   // stream host function, so the exchange stays asynchronous like RCCL's
@@ -5815,7 +5815,7 @@ struct Engine::Impl {
   uint32_t stat_chunk_cap = 0;  // diagnostic: cap on the static chunk (pods, multiple of KSG_BATCH)
   uint32_t n_cus = 256;  // compute units of the device
   hipStream_t sstream = nullptr;  // low-priority side stream (static records of the window path)
-  hipStream_t rstream = nullptr, xstream = nullptr;  // sharded windows: replay / exchange streams (run_batches_split)
+  hipStream_t rstream = nullptr, xstream = nullptr;  // sharded windows: replay / exchange streams (window_split)
   hipEvent_t xg[2] = {nullptr, nullptr}, xr[2] = {nullptr, nullptr}, xe[2] = {nullptr, nullptr}, xjoin = nullptr;
   // the side kernel beside the persistent loop (k_static_dec_run): its records done / the side stream free to start
   hipEvent_t sev_ready = nullptr, sev_free = nullptr;
@@ -6336,13 +6336,16 @@ static uint32_t prog_need_of(const ksg_prog* h) {
 // some of its launches with a pair of I.sev events.  Which launches is each
 // site's own `gate`; a launch is sampled when sampling is on, its gate holds
 // and a pair is left.
-static bool ensure_sample_events(Engine::Impl& I, size_t n_events, std::string& err) {
-  while (I.sample_every && I.sev.size() < n_events) {
+static bool ensure_sample_events(Engine::Impl& I, std::vector<hipEvent_t>& sev, size_t n_events, std::string& err) {
+  while (I.sample_every && sev.size() < n_events) {
     hipEvent_t e;
     HIPCHK(hipEventCreate(&e));
-    I.sev.push_back(e);
+    sev.push_back(e);
   }
   return true;
+}
+static bool ensure_sample_events(Engine::Impl& I, size_t n_events, std::string& err) {
+  return ensure_sample_events(I, I.sev, n_events, err);
 }
 static bool every_nth(const Engine::Impl& I, uint32_t j) { return I.sample_every && (j % I.sample_every) == 0; }
 static bool sample_begin(Engine::Impl& I, hipStream_t s, bool gate, bool& sampled, std::string& err) {
@@ -6373,21 +6376,28 @@ static void kept_outputs(const Engine::Impl& I, uint32_t j, DevOut& O) {
 // 1 go, 2 not co-resident (its blocks left untouched), 3 an earlier launch of the
 // call aborted; 0 with err set: the launch never decided (state lost).
 static uint32_t wait_verdict(Engine::Impl& I, hipStream_t s, std::string& err);
-// Windows of KSG_BATCH pods, one k_window launch each (see the kernel): launch
-// j evaluates window j+1 and replays window j; the sharded path all-gathers
-// each window's candidate records between launches.
+// The pinned verdict block of the context's first persistent launch, and the first clear of the whole RunSync.
+static bool ensure_verdict(Engine::Impl& I, hipStream_t s, std::string& err) {
+  if (I.hverdict) return true;
+  HIPCHK(hipHostMalloc((void**)&I.hverdict, kVerdictBytes, hipHostMallocCoherent | hipHostMallocMapped));
+  HIPCHK(hipMemsetAsync(I.rsync.p, 0, sizeof(RunSync), s));  // (the sticky abort word starts clear)
+  return true;
+}
+// What became of the launch: it ran; it left at the handshake (its blocks were not
+// all resident and touched nothing: the caller's fallback); or an error (err set;
+// `what` names the launch when an earlier one aborted and the state is not valid).
+enum class Verdict { kRan, kLeft, kError };
+static Verdict persistent_verdict(Engine::Impl& I, hipStream_t s, const char* what, std::string& err) {
+  const uint32_t v = wait_verdict(I, s, err);
+  if (v == 3u) {
+    I.lost = true;
+    err = std::string(what) + ": a gate never completed (blocks not co-resident?)";
+  }
+  return v == 1u ? Verdict::kRan : v == 2u ? Verdict::kLeft : Verdict::kError;
+}
 static bool xgather(Engine::Impl& I, size_t bytes, std::string& err, const uint8_t* src = nullptr,
                     hipStream_t st = nullptr);
 static bool tables_ready(Engine::Impl& I, std::string& err);
-// Sharded windows, split over three streams so that the exchange leaves the
-// replay's critical path.  Window j's evaluation (eval-only k_window launch,
-// engine stream) needs the rows as of the end of window j-2, i.e. only the
-// replay of j-2; its all-gather and merge run on the exchange stream; the
-// replay of j (replay-only launch, replay stream) waits for the merge of j.
-// Per window: max(eval, exchange, replay) instead of their sum.  Buffer reuse is
-// ordered by those waits: window j's tile lists, send buffer, output-ring slots
-// and P-list slot are those of window j-2, whose replay it waited for (and that
-// replay waited for j-2's exchange).
 // The window kernels [static records][default Fit/BA arguments], and their dynamic LDS size set once.
 static void (*const kWindow[2][2])(DevCluster, DevProfile, WinArgs) = {{k_window<0, false>, k_window<1, false>},
                                                                        {k_window<0, true>, k_window<1, true>}};
@@ -6401,120 +6411,63 @@ static bool window_lds_attr(std::string& err) {
   done = true;
   return true;
 }
-static bool run_batches_split(Engine::Impl& I, const WinArgs& A0, uint32_t first, uint32_t count, uint32_t T,
-                              std::string& err) {
-  hipStream_t s = I.stream;
-  DevCluster C = I.cluster();
-  if (!I.rstream) {
-    HIPCHK(hipStreamCreateWithFlags(&I.rstream, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&I.xstream, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&I.xg[0], &I.xg[1], &I.xr[0], &I.xr[1], &I.xe[0], &I.xe[1], &I.xjoin})
-      HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-  }
-  hipStream_t sr = I.rstream, sx = I.xstream;
-  if (!I.xsend.grow(2 * kRecBytes, 0, s, err)) return false;  // one send record per window parity
-  HIPCHK(hipEventRecord(I.xjoin, s));  // the other streams start after the run's set-up
-  HIPCHK(hipStreamWaitEvent(sr, I.xjoin, 0));
-  HIPCHK(hipStreamWaitEvent(sx, I.xjoin, 0));
-  const uint32_t nwin = (count + KSG_BATCH - 1) / KSG_BATCH;
-  const size_t tt_sz = (size_t)KSG_BATCH * T * KSG_TOPK, tf_sz = (size_t)KSG_BATCH * T * 3;
-  const dim3 blk(KSG_WIN_THREADS);
-  auto launch = [&](hipStream_t st, const WinArgs& a, uint32_t blocks) {
-    hipLaunchKernelGGL(kWindow[0][I.eval_mode == 1], dim3(blocks), blk, sizeof(WinLDS), st, C, I.F, a);
-  };
-  for (int64_t j = 0; j <= (int64_t)nwin; ++j) {
-    if (j < (int64_t)nwin) {  // evaluation of window E = j, exchange, merge (engine stream)
-      const int64_t E = j, P = E - 2;
-      WinArgs a = A0;
-      a.nw = 0;
-      a.stamps = nullptr;
-      a.e0 = first + (uint32_t)E * KSG_BATCH;
-      a.ne = std::min<uint32_t>(KSG_BATCH, first + count - a.e0);
-      a.tile_top = I.tile_top.p + (size_t)(E & 1) * tt_sz;
-      a.tile_feas = I.tfeas.p + (size_t)(E & 1) * tf_sz;
-      a.erec = I.xsend.p + (size_t)(E & 1) * kRecBytes;
-      a.estamps = I.stamps_on ? I.stamps.p + (size_t)E * 32 : nullptr;
-      a.pprev = I.pend.p + (size_t)(P & 1) * KSG_BATCH;
-      a.pprev_n = I.pend_n.p + (P & 1);
-      if (E >= 2) HIPCHK(hipStreamWaitEvent(s, I.xr[E & 1], 0));  // the replay of E-2
-      bool sampled;
-      if (!sample_begin(I, s, true, sampled, err)) return false;
-      launch(s, a, 1 + a.ne * T);
-      if (!sample_end(I, s, sampled, err)) return false;
-      HIPCHK(hipEventRecord(I.xe[E & 1], s));
-      HIPCHK(hipStreamWaitEvent(sx, I.xe[E & 1], 0));
-      if (!xgather(I, kXchgBytes, err, a.erec, sx)) return false;
-      hipLaunchKernelGGL(k_window_gmerge, dim3(a.ne), dim3(64), 0, sx, I.xrecv.p, I.xranks, I.xrows.p, a.pprev,
-                         a.pprev_n, I.wrec.p + (size_t)(E & 1) * kRecBytes);
-      HIPCHK(hipEventRecord(I.xg[E & 1], sx));
-    }
-    if (j >= 1) {  // replay of window W = j - 1 (replay stream)
-      const int64_t W = j - 1, P = W - 1;
-      WinArgs a = A0;
-      a.ne = 0;
-      a.estamps = nullptr;
-      a.w0 = first + (uint32_t)W * KSG_BATCH;
-      a.nw = std::min<uint32_t>(KSG_BATCH, first + count - a.w0);
-      a.wrec = I.wrec.p + (size_t)(W & 1) * kRecBytes;
-      a.pnext = I.pend.p + (size_t)(W & 1) * KSG_BATCH;
-      a.pnext_n = I.pend_n.p + (W & 1);
-      a.pprev = I.pend.p + (size_t)(P & 1) * KSG_BATCH;
-      a.pprev_n = I.pend_n.p + (P & 1);
-      a.stamps = I.stamps_on ? I.stamps.p + (size_t)W * 32 : nullptr;
-      HIPCHK(hipStreamWaitEvent(sr, I.xg[W & 1], 0));  // its merged candidates
-      launch(sr, a, 1);
-      HIPCHK(hipEventRecord(I.xr[W & 1], sr));
-    }
-  }
-  if (nwin) {
-    const int64_t L = nwin - 1;
-    hipLaunchKernelGGL(k_apply_pend, dim3(1), dim3(KSG_BATCH), 0, sr, C, I.pend.p + (size_t)(L & 1) * KSG_BATCH,
-                       I.pend_n.p + (L & 1));
-  }
-  HIPCHK(hipEventRecord(I.xjoin, sr));  // everything after the run waits on the engine stream
-  HIPCHK(hipStreamWaitEvent(s, I.xjoin, 0));  // (the replay stream's last wait covers the exchange stream)
-  HIPCHK(hipEventRecord(I.ev1, s));
-  HIPCHK(hipGetLastError());
-  return true;
+
+// ---- The window path (run_batches): the split loop of a sharded run without
+// static records; otherwise the persistent loop when it may run, and the
+// launch-per-window loop when it may not or when it left at its handshake.
+// WindowRun: the state of one call that the paths share.
+struct WindowRun {
+  uint32_t first, count;
+  hipStream_t s;
+  uint32_t nwin, T;      // windows; eval tiles per pod
+  size_t tt_sz, tf_sz;   // one window's tile lists (tile_top, tile_feas)
+  bool sharded;          // node-sharded: candidate records all-gathered per window
+  bool stat, gstat;      // static records (Taint / NodeAffinity profiles); over every node of a sharded run
+  bool stat_run, persist;  // every record of the run in one chunk; the persistent loop may run
+  uint32_t chunk, nslots, SN;  // the record ring: nslots chunks of `chunk` pods, SN nodes per pod
+  DevCluster C, CS;      // the cluster; as the static-record kernels see it
+  WinArgs A;             // what every launch shares (no window: ne = nw = 0, no stamps)
+};
+
+// k_static's grid: node tiles x pod groups.
+static dim3 static_grid(uint32_t nodes, uint32_t pods) {
+  return dim3(std::max<uint32_t>((nodes + 256 * KSG_ST_NPT - 1) / (256 * KSG_ST_NPT), 1), (pods + KSG_ST_PODS - 1) / KSG_ST_PODS);
 }
-static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::string& err) {
-  if (I.R > 4) { err = "batch path supports at most 4 resource columns"; return false; }
-  hipStream_t s = I.stream;
-  DevCluster C = I.cluster();
+// k_static_dec_run's node tiles (1,024-thread blocks).
+static uint32_t static_run_tiles(uint32_t n) { return std::max<uint32_t>((n + 1024 * KSG_SD_NPT - 1) / (1024 * KSG_SD_NPT), 1); }
+
+// Fills W: the shared arguments, a sharded run's row replica, the record ring, which loop may run.
+static bool window_setup(Engine::Impl& I, WindowRun& W, std::string& err) {
+  const uint32_t first = W.first, count = W.count;
+  hipStream_t s = W.s;
+  const DevCluster C = W.C = I.cluster();
   // nodes per eval thread: enough that one window's eval blocks fit the CUs
   // beside the replay block in one round (one 1,024-thread block per CU)
-  const uint32_t T = eval_tiles(I.N, I.n_cus), npt = eval_npt(I.N, I.n_cus), tile_len = npt * KSG_TILE;
-  const uint32_t nwin = (count + KSG_BATCH - 1) / KSG_BATCH;
+  const uint32_t T = W.T = eval_tiles(I.N, I.n_cus), npt = eval_npt(I.N, I.n_cus), tile_len = npt * KSG_TILE;
+  const uint32_t nwin = W.nwin = (count + KSG_BATCH - 1) / KSG_BATCH;
   if (!ensure_sample_events(I, 2 * ((size_t)nwin + 2), err)) return false;
-  I.n_samples = 0;
-  I.n_st = 0;
+  I.n_samples = I.n_st = 0;
   I.stat_pods_sampled = 0;
   if (!window_lds_attr(err)) return false;
   HIPCHK(hipEventRecord(I.ev0, s));
   HIPCHK(hipMemsetAsync(I.pend_n.p, 0, 2 * sizeof(int32_t), s));
-  WinArgs A{};
+  WinArgs& A = W.A = WinArgs{};
   A.plite = I.plite.p;
-  A.first = first;
-  A.keep_first = I.keep_first;
-  A.keep_n = I.keep_n;
+  A.first = first; A.keep_first = I.keep_first; A.keep_n = I.keep_n;
   A.need_eph = I.any_eph_req ? 1u : 0u;
   A.kfilter = I.kfilter.p; A.kscore = I.kscore.p; A.ktotal = I.ktotal.p;
   A.sfilter = I.bfilter.p; A.sscore = I.bscore.p; A.stotal = I.btotal.p;
-  A.T = T;
-  A.npt = npt;
-  A.tile_len = tile_len;
+  A.T = T; A.npt = npt; A.tile_len = tile_len;
   // (a tile merge deferred to the replay block was measured slower on cfg2 and
   // cfg3 and removed: merging 32 pods' tile lists cost the replay block ~9 us,
   // more than the evaluation's own merge costs its chain)
   A.stash_npt = kStashNpt;
-  const size_t tt_sz = (size_t)KSG_BATCH * T * KSG_TOPK, tf_sz = (size_t)KSG_BATCH * T * 3;
-  A.tile_top = I.tile_top.p;
-  A.tile_feas = I.tfeas.p;
-  A.arrive = I.arrive.p;
-  A.astride = 1;
+  W.tt_sz = (size_t)KSG_BATCH * T * KSG_TOPK;
+  W.tf_sz = (size_t)KSG_BATCH * T * 3;
+  A.tile_top = I.tile_top.p; A.tile_feas = I.tfeas.p;
+  A.arrive = I.arrive.p; A.astride = 1;
   A.sums = I.sums.p;
-  const bool sharded = I.xranks > 1;
-  A.xrows = nullptr;
+  const bool sharded = W.sharded = I.xranks > 1;
   if (sharded) {  // every node's row on every rank (kXchgBytes exchanges: keys only)
     const uint32_t G = std::max<uint32_t>(I.G, 1), stride = (G + I.xranks - 1) / I.xranks;
     if (!I.xrows.alloc(G, err)) return false;
@@ -6533,14 +6486,14 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
   // on the engine stream just before the launch that evaluates its first window.
   // (Chunks computed two ahead on the side stream, beside the window launches,
   // were measured no faster — the windows slow down beside them — and removed.)
-  const bool stat = I.batch_static;
+  const bool stat = W.stat = I.batch_static;
   // the persistent window loop over static records: every record of the run
   // computed before the launch (one chunk; the loop has no ring to roll), when
   // they fit KSG_STATIC_RUN_MB (default 16 GiB of the 288 GB)
   const bool persist_ok = !sharded && I.win_run_on && nwin > 0 && 1 + (uint64_t)KSG_BATCH * T <= I.n_cus;
   const uint32_t count32 = (count + KSG_BATCH - 1) / KSG_BATCH * KSG_BATCH;
   const uint64_t run_bytes = (uint64_t)count32 * std::max<uint32_t>(I.N, 1) * sizeof(StaticRec);
-  bool stat_run = stat && persist_ok && I.static_run_mb > 0 && !I.stat_chunk_cap &&
+  bool& stat_run = W.stat_run = stat && persist_ok && I.static_run_mb > 0 && !I.stat_chunk_cap &&
                   run_bytes <= ((uint64_t)I.static_run_mb << 20);
   if (stat_run && run_bytes > I.stat.n * sizeof(StaticRec)) {
     // (a run-sized buffer only while it leaves most of the device free: another
@@ -6551,252 +6504,311 @@ static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::st
       stat_run = false;
     }
   }
-  uint32_t chunk = 0, nslots = 2;
-  const bool gstat = stat && I.gstat && sharded;  // node-sharded: records over every node
-  const DevCluster CS = gstat ? I.cluster_static() : C;
-  const uint32_t SN = gstat ? I.G : I.N;
+  uint32_t &chunk = W.chunk, &nslots = W.nslots;
+  const bool gstat = W.gstat = stat && I.gstat && sharded;  // node-sharded: records over every node
+  W.CS = gstat ? I.cluster_static() : C;
+  const uint32_t SN = W.SN = gstat ? I.G : I.N;
   A.stat_n = std::max<uint32_t>(SN, 1);
   A.stat_base = gstat ? 0 : I.goff;
   A.G = I.G;
   if (stat) {
     const size_t Nn = std::max<uint32_t>(SN, 1);
-    auto size_ring = [&]() {
+    for (;;) {  // (a second time when the run-sized buffer does not fit after all: the ring)
       nslots = stat_run ? 1 : 2;
       const size_t budget = (size_t)64 << 20;
       chunk = (uint32_t)std::max<size_t>(KSG_BATCH, (budget / (Nn * sizeof(StaticRec))) / KSG_BATCH * KSG_BATCH);
       chunk = std::min<uint32_t>(chunk, count32);
       if (I.stat_chunk_cap) chunk = std::min<uint32_t>(chunk, I.stat_chunk_cap);  // tests: force ring roll-over
       if (stat_run) chunk = count32;
-    };
-    size_ring();
-    if (!I.stat.alloc((size_t)nslots * chunk * Nn, err)) {
+      if (I.stat.alloc((size_t)nslots * chunk * Nn, err)) break;
       if (!stat_run) return false;
-      (void)hipGetLastError();  // (the run-sized buffer did not fit after all: the ring)
+      (void)hipGetLastError();
       stat_run = false;
-      size_ring();
-      if (!I.stat.alloc((size_t)nslots * chunk * Nn, err)) return false;
     }
     if (!I.mpred.alloc(2 * (size_t)std::max<uint32_t>(count, 1), err)) return false;
     A.stat = I.stat.p;
     A.stat_ring = nslots * chunk;
     A.mpred = I.mpred.p;
   }
-  // decoded pods (k_static_dec) when every pod of the chunk flattens and the
-  // nodes' taints fit the id set (KSG_STATIC_DEC=0: the program-walking k_static)
-  auto static_dec_ok = [&](uint32_t q0, uint32_t cn) {
-    bool dec = I.static_dec && I.max_taints <= 4 && I.max_tid < 64 && !I.taint_dup;
-    for (uint32_t q = q0; dec && q < q0 + cn; ++q) dec = need::decodable(I.prog_need[q]);
-    return dec;
-  };
-  // ready: k_static_dec beside the persistent loop, counting its pod groups there
-  // (the maxima already reset on the engine stream)
-  auto issue_static = [&](uint32_t c, hipStream_t st, uint32_t* ready = nullptr, uint32_t run_grid = 0,
-                          uint32_t* arrive = nullptr) -> bool {
-    const uint32_t q0 = first + c * chunk, cn = std::min(chunk, first + count - q0);
-    if (!ready)
-      HIPCHK(hipMemsetAsync(I.mpred.p + 2 * (size_t)(q0 - first), 0xFF, 2 * (size_t)cn * sizeof(int64_t), st));
-    const dim3 sgrid(std::max<uint32_t>((SN + 256 * KSG_ST_NPT - 1) / (256 * KSG_ST_NPT), 1),
-                     (cn + KSG_ST_PODS - 1) / KSG_ST_PODS);
-    const bool ssamp = I.sample_every && (st == s || ready);
-    if (ssamp) {
-      while (I.sev_st.size() < 2 * (size_t)(I.n_st + 1)) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        I.sev_st.push_back(e);
-      }
-      HIPCHK(hipEventRecord(I.sev_st[2 * I.n_st], st));
-    }
-    StaticRec* const sout = I.stat.p + (size_t)((q0 - first) % (nslots * chunk)) * A.stat_n;
-    const bool dec = static_dec_ok(q0, cn);
-    if (ready && !dec) { err = "static records beside the loop: pods that do not decode"; return false; }
-    if (dec) {
-      if (!I.sd_pods.alloc((size_t)chunk * (sizeof(WcPod) / 8), err)) return false;
-      WcPod* wp = reinterpret_cast<WcPod*>(I.sd_pods.p);
-      hipLaunchKernelGGL(k_st_decode, dim3((cn + 63) / 64), dim3(64), 0, st, CS, I.F, I.progs.p, I.prog_off_d.p, q0, cn,
-                         wp, gstat ? 1 : 0);
-      const dim3 dgrid(std::max<uint32_t>((SN + 256 * KSG_SD_NPT - 1) / (256 * KSG_SD_NPT), 1),
-                       (cn + KSG_SD_PODS - 1) / KSG_SD_PODS);
-      if (run_grid) {  // (beside the persistent loop: a few 1,024-thread blocks walking the items)
-        const uint32_t ntx = std::max<uint32_t>((SN + 1024 * KSG_SD_NPT - 1) / (1024 * KSG_SD_NPT), 1);
-        const uint32_t items = ntx * ((cn + KSG_SD_PODS - 1) / KSG_SD_PODS);
-        hipLaunchKernelGGL(k_static_dec_run, dim3(std::min(run_grid, items)), dim3(1024), 0, st, CS, I.F, wp, I.progs.p, cn,
-                           sout, I.mpred.p + 2 * (size_t)(q0 - first), ready, ntx, items, arrive);
-      } else {
-        hipLaunchKernelGGL(k_static_dec, dgrid, dim3(256), 0, st, CS, I.F, wp, I.progs.p, cn, sout,
-                           I.mpred.p + 2 * (size_t)(q0 - first), ready);
-      }
-      I.static_dec_chunks++;
+  W.persist = persist_ok && (!stat || stat_run);
+  return true;
+}
+
+// decoded pods (k_static_dec) when every pod of the chunk flattens and the
+// nodes' taints fit the id set (KSG_STATIC_DEC=0: the program-walking k_static)
+static bool static_dec_ok(const Engine::Impl& I, uint32_t q0, uint32_t cn) {
+  bool dec = I.static_dec && I.max_taints <= 4 && I.max_tid < 64 && !I.taint_dup;
+  for (uint32_t q = q0; dec && q < q0 + cn; ++q) dec = need::decodable(I.prog_need[q]);
+  return dec;
+}
+// Where a chunk's records are computed: on stream st, before the launch that
+// reads them; or beside the persistent loop: k_static_dec_run, side_grid blocks
+// that count the pod groups and themselves in I.sready (the maxima already reset).
+struct StaticWhere {
+  hipStream_t st;
+  uint32_t side_grid = 0;  // 0: before
+};
+// The static records and maxima of chunk c of the ring.
+static bool window_static(Engine::Impl& I, const WindowRun& W, uint32_t c, StaticWhere where, std::string& err) {
+  const uint32_t first = W.first, chunk = W.chunk, SN = W.SN;
+  const DevCluster& CS = W.CS;
+  const bool gstat = W.gstat, beside = where.side_grid != 0;
+  hipStream_t st = where.st;
+  const uint32_t q0 = first + c * chunk, cn = std::min(chunk, first + W.count - q0);
+  const uint32_t groups = (cn + KSG_SD_PODS - 1) / KSG_SD_PODS;
+  if (!beside)
+    HIPCHK(hipMemsetAsync(I.mpred.p + 2 * (size_t)(q0 - first), 0xFF, 2 * (size_t)cn * sizeof(int64_t), st));
+  const bool ssamp = I.sample_every && (st == W.s || beside);
+  if (ssamp) {
+    if (!ensure_sample_events(I, I.sev_st, 2 * (size_t)(I.n_st + 1), err)) return false;
+    HIPCHK(hipEventRecord(I.sev_st[2 * I.n_st], st));
+  }
+  StaticRec* const sout = I.stat.p + (size_t)((q0 - first) % (W.nslots * chunk)) * W.A.stat_n;
+  int64_t* const mpred = I.mpred.p + 2 * (size_t)(q0 - first);
+  const bool dec = static_dec_ok(I, q0, cn);
+  if (beside && !dec) { err = "static records beside the loop: pods that do not decode"; return false; }
+  if (dec) {
+    if (!I.sd_pods.alloc((size_t)chunk * (sizeof(WcPod) / 8), err)) return false;
+    WcPod* wp = reinterpret_cast<WcPod*>(I.sd_pods.p);
+    hipLaunchKernelGGL(k_st_decode, dim3((cn + 63) / 64), dim3(64), 0, st, CS, I.F, I.progs.p, I.prog_off_d.p, q0, cn,
+                       wp, gstat ? 1 : 0);
+    if (beside) {  // (a few 1,024-thread blocks walking the items)
+      const uint32_t ntx = static_run_tiles(SN), items = ntx * groups;
+      hipLaunchKernelGGL(k_static_dec_run, dim3(std::min(where.side_grid, items)), dim3(1024), 0, st, CS, I.F, wp, I.progs.p,
+                         cn, sout, mpred, I.sready.p, ntx, items, I.sready.p + groups);
     } else {
-      hipLaunchKernelGGL(k_static, sgrid, dim3(256), 0, st, CS, I.F, I.progs.p, I.prog_off_d.p, q0, cn, sout,
-                         I.mpred.p + 2 * (size_t)(q0 - first), gstat ? 1 : 0);
+      const dim3 dgrid(std::max<uint32_t>((SN + 256 * KSG_SD_NPT - 1) / (256 * KSG_SD_NPT), 1), groups);
+      hipLaunchKernelGGL(k_static_dec, dgrid, dim3(256), 0, st, CS, I.F, wp, I.progs.p, cn, sout, mpred, (uint32_t*)nullptr);
     }
-    if (ssamp) {
-      HIPCHK(hipEventRecord(I.sev_st[2 * I.n_st + 1], st));
-      I.stat_pods_sampled += cn;
-      I.n_st++;
+    I.static_dec_chunks++;
+  } else {
+    hipLaunchKernelGGL(k_static, static_grid(SN, cn), dim3(256), 0, st, CS, I.F, I.progs.p, I.prog_off_d.p, q0, cn, sout,
+                       mpred, gstat ? 1 : 0);
+  }
+  if (ssamp) {
+    HIPCHK(hipEventRecord(I.sev_st[2 * I.n_st + 1], st));
+    I.stat_pods_sampled += cn;
+    I.n_st++;
+  }
+  return true;
+}
+
+// The arguments of window E's evaluation and of window Wn's replay, for both
+// host loops (k_window_run derives the same on the device).  erec: where the
+// evaluation leaves its candidate record.  P: the P list it overrides rows from:
+// E-2 in an eval-only launch; in a fused launch the replay's Wn-1, the same number.
+static void win_eval_args(const Engine::Impl& I, const WindowRun& W, WinArgs& a, int64_t E, uint8_t* erec, int64_t P) {
+  a.e0 = W.first + (uint32_t)E * KSG_BATCH;
+  a.ne = std::min<uint32_t>(KSG_BATCH, W.first + W.count - a.e0);
+  a.tile_top = I.tile_top.p + (size_t)(E & 1) * W.tt_sz; a.tile_feas = I.tfeas.p + (size_t)(E & 1) * W.tf_sz;
+  a.estamps = I.stamps_on ? I.stamps.p + (size_t)E * 32 : nullptr;
+  a.erec = erec;
+  a.pprev = I.pend.p + (size_t)(P & 1) * KSG_BATCH; a.pprev_n = I.pend_n.p + (P & 1);
+}
+static void win_replay_args(const Engine::Impl& I, const WindowRun& W, WinArgs& a, int64_t Wn) {
+  const int64_t P = Wn - 1;
+  a.w0 = W.first + (uint32_t)Wn * KSG_BATCH;
+  a.nw = std::min<uint32_t>(KSG_BATCH, W.first + W.count - a.w0);
+  a.wrec = I.wrec.p + (size_t)(Wn & 1) * kRecBytes;
+  a.pnext = I.pend.p + (size_t)(Wn & 1) * KSG_BATCH; a.pnext_n = I.pend_n.p + (Wn & 1);
+  a.stamps = I.stamps_on ? I.stamps.p + (size_t)Wn * 32 : nullptr;
+  a.pprev = I.pend.p + (size_t)(P & 1) * KSG_BATCH; a.pprev_n = I.pend_n.p + (P & 1);
+}
+
+// Sharded windows, split over three streams so that the exchange leaves the
+// replay's critical path.  Window j's evaluation (eval-only k_window launch,
+// engine stream) needs the rows as of the end of window j-2, i.e. only the
+// replay of j-2; its all-gather and merge run on the exchange stream; the
+// replay of j (replay-only launch, replay stream) waits for the merge of j.
+// Per window: max(eval, exchange, replay) instead of their sum.  Buffer reuse is
+// ordered by those waits: window j's tile lists, send buffer, output-ring slots
+// and P-list slot are those of window j-2, whose replay it waited for (and that
+// replay waited for j-2's exchange).  The tail runs on the replay stream.
+static bool window_split(Engine::Impl& I, const WindowRun& W, std::string& err) {
+  hipStream_t s = W.s;
+  if (!I.rstream) {
+    HIPCHK(hipStreamCreateWithFlags(&I.rstream, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(&I.xstream, hipStreamNonBlocking));
+    for (hipEvent_t* e : {&I.xg[0], &I.xg[1], &I.xr[0], &I.xr[1], &I.xe[0], &I.xe[1], &I.xjoin})
+      HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  }
+  hipStream_t sr = I.rstream, sx = I.xstream;
+  if (!I.xsend.grow(2 * kRecBytes, 0, s, err)) return false;  // one send record per window parity
+  HIPCHK(hipEventRecord(I.xjoin, s));  // the other streams start after the run's set-up
+  HIPCHK(hipStreamWaitEvent(sr, I.xjoin, 0));
+  HIPCHK(hipStreamWaitEvent(sx, I.xjoin, 0));
+  const dim3 blk(KSG_WIN_THREADS);
+  for (int64_t j = 0; j <= (int64_t)W.nwin; ++j) {
+    const int64_t E = j, Wn = j - 1;
+    if (E < (int64_t)W.nwin) {  // evaluation of window E, exchange, merge (engine stream)
+      WinArgs a = W.A;
+      win_eval_args(I, W, a, E, I.xsend.p + (size_t)(E & 1) * kRecBytes, E - 2);
+      if (E >= 2) HIPCHK(hipStreamWaitEvent(s, I.xr[E & 1], 0));  // the replay of E-2
+      bool sampled;
+      if (!sample_begin(I, s, true, sampled, err)) return false;
+      hipLaunchKernelGGL(kWindow[0][I.eval_mode == 1], dim3(1 + a.ne * W.T), blk, sizeof(WinLDS), s, W.C, I.F, a);
+      if (!sample_end(I, s, sampled, err)) return false;
+      HIPCHK(hipEventRecord(I.xe[E & 1], s));
+      HIPCHK(hipStreamWaitEvent(sx, I.xe[E & 1], 0));
+      if (!xgather(I, kXchgBytes, err, a.erec, sx)) return false;
+      hipLaunchKernelGGL(k_window_gmerge, dim3(a.ne), dim3(64), 0, sx, I.xrecv.p, I.xranks, I.xrows.p, a.pprev,
+                         a.pprev_n, I.wrec.p + (size_t)(E & 1) * kRecBytes);
+      HIPCHK(hipEventRecord(I.xg[E & 1], sx));
     }
+    if (Wn >= 0) {  // replay of window Wn (replay stream)
+      WinArgs a = W.A;
+      win_replay_args(I, W, a, Wn);
+      HIPCHK(hipStreamWaitEvent(sr, I.xg[Wn & 1], 0));  // its merged candidates
+      hipLaunchKernelGGL(kWindow[0][I.eval_mode == 1], dim3(1), blk, sizeof(WinLDS), sr, W.C, I.F, a);
+      HIPCHK(hipEventRecord(I.xr[Wn & 1], sr));
+    }
+  }
+  return true;
+}
+
+// The persistent window loop: one launch for every window.  ran: it ran; else
+// its blocks were not all resident and left untouched: the launch-per-window loop.
+static bool window_persistent(Engine::Impl& I, const WindowRun& W, bool& ran, std::string& err) {
+  hipStream_t s = W.s;
+  const uint32_t first = W.first, count = W.count;
+  ran = false;
+  // (two replay blocks when the extra block fits as well)
+  const bool r2 = (W.stat ? I.win_replay2_stat : I.win_replay2) && 2 + (uint64_t)KSG_BATCH * W.T <= I.n_cus;
+  const uint32_t grid = (r2 ? 2u : 1u) + KSG_BATCH * W.T;
+  // the run's records: before the launch, or (KSG_STATIC_OVERLAP, default)
+  // beside it — k_static_dec_run, one 1,024-thread block per CU the loop leaves
+  // idle, launched on the side stream BEFORE the loop; the eval blocks wait per
+  // window for their pods' groups (win_stat_gate).  The side blocks count
+  // themselves in and the loop's handshake goes only once all of them have
+  // started; else it leaves before any state changes ("Window path").
+  const uint32_t side_grid = I.n_cus > grid ? I.n_cus - grid : 0;
+  const bool overlap = W.stat_run && I.static_overlap && I.sstream && side_grid > 0 && static_dec_ok(I, first, count);
+  const uint32_t sgroups = (count + KSG_SD_PODS - 1) / KSG_SD_PODS;
+  // the side kernel; tests (KSG_STATIC_BESIDE_TEST) launch it after the loop or after its verdict
+  auto issue_side = [&](int when) -> bool {
+    if (!overlap || I.static_beside_test != when) return true;
+    if (!window_static(I, W, 0, StaticWhere{I.sstream, side_grid}, err)) return false;
+    HIPCHK(hipEventRecord(I.sev_ready, I.sstream));
     return true;
   };
-  if (sharded && !stat) return run_batches_split(I, A, first, count, T, err);
-  // the persistent window loop: one launch for every window (its blocks all
-  // resident: one per CU); not co-resident -> the launch-per-window loop below
-  if (persist_ok && (!stat || stat_run)) {
-    // (two replay blocks when the extra block fits as well)
-    const bool r2 = (stat ? I.win_replay2_stat : I.win_replay2) && 2 + (uint64_t)KSG_BATCH * T <= I.n_cus;
-    const uint32_t nrep = r2 ? 2u : 1u;
-    const uint32_t grid = nrep + KSG_BATCH * T;
-    // the run's records: before the launch, or (KSG_STATIC_OVERLAP, default)
-    // beside it — k_static_dec_run, one 1,024-thread block per CU the loop leaves
-    // idle, launched on the side stream BEFORE the loop (its blocks then hold
-    // those CUs and the loop's take the rest; kernels run one at a time, as under
-    // a PMC pass, it simply completes first); the eval blocks wait per window for
-    // their pods' groups (win_stat_gate).  The side blocks count themselves in
-    // (one word after the groups' counters) and the loop's handshake goes only
-    // once all of them have started: side blocks that never become resident
-    // beside the loop send it to the per-window fallback before any state changes,
-    // instead of a gate running out mid-run.
-    const uint32_t side_grid = I.n_cus > grid ? I.n_cus - grid : 0;
-    const bool overlap = stat_run && I.static_overlap && I.sstream && side_grid > 0 && static_dec_ok(first, count);
-    const uint32_t sgroups = (count + KSG_SD_PODS - 1) / KSG_SD_PODS;
-    uint32_t side_blocks = 0;
-    auto issue_side = [&]() -> bool {
-      if (!issue_static(0, I.sstream, I.sready.p, side_grid, I.sready.p + sgroups)) return false;
-      HIPCHK(hipEventRecord(I.sev_ready, I.sstream));
-      return true;
-    };
-    if (overlap) {
-      const uint32_t ntx = std::max<uint32_t>((SN + 1024 * KSG_SD_NPT - 1) / (1024 * KSG_SD_NPT), 1);
-      side_blocks = std::min<uint32_t>(side_grid, ntx * sgroups);
-      if (!I.sready.alloc(sgroups + 1, err) || !I.sd_pods.alloc((size_t)chunk * (sizeof(WcPod) / 8), err)) return false;
-      HIPCHK(hipMemsetAsync(I.sready.p, 0, (sgroups + 1) * sizeof(uint32_t), s));
-      HIPCHK(hipMemsetAsync(I.mpred.p, 0xFF, 2 * (size_t)count * sizeof(int64_t), s));
-      if (!I.sev_ready)
-        for (auto* e : {&I.sev_ready, &I.sev_free})
-          HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-      HIPCHK(hipEventRecord(I.sev_free, s));
-      HIPCHK(hipStreamWaitEvent(I.sstream, I.sev_free, 0));
-      if (I.static_beside_test == 0 && !issue_side()) return false;
-    } else if (stat_run && !issue_static(0, s)) {  // (every record of the run)
-      return false;
-    }
-    if (!I.wsync.alloc(1, err) || !I.rsync.alloc(1, err)) return false;
-    if (!I.hverdict) {
-      HIPCHK(hipHostMalloc((void**)&I.hverdict, kVerdictBytes, hipHostMallocCoherent | hipHostMallocMapped));
-      HIPCHK(hipMemsetAsync(I.rsync.p, 0, sizeof(RunSync), s));  // (the sticky abort word starts clear)
-    }
-    HIPCHK(hipMemsetAsync(I.wsync.p, 0, sizeof(WinSync), s));
-    HIPCHK(hipMemsetAsync(I.rsync.p, 0, kRunSyncReset, s));
-    HIPCHK(hipMemsetAsync(I.arrive.p, 0, 2 * KSG_BATCH * 32 * sizeof(uint32_t), s));
-    // (every entry of both P lists starts unused: node -1, which the eval blocks
-    // read in place of a count; the per-window loop, on a fallback, goes by pend_n)
-    HIPCHK(hipMemsetAsync(I.pend.p, 0xFF, 2 * KSG_BATCH * sizeof(Pend), s));
-    WinRunArgs R{};
-    R.nwin = nwin;
-    R.first = first;
-    R.count = count;
-    R.T = T;
-    R.tt_sz = (uint32_t)tt_sz;
-    R.tf_sz = (uint32_t)tf_sz;
-    R.tile_top = I.tile_top.p;
-    R.tfeas = I.tfeas.p;
-    R.wrec = I.wrec.p;
-    R.pend = I.pend.p;
-    R.pend_n = I.pend_n.p;
-    R.arrive = I.arrive.p;
-    R.stamps = I.stamps_on ? I.stamps.p : nullptr;
-    R.sready = overlap ? I.sready.p : nullptr;
-    R.sready_need = std::max<uint32_t>((SN + 1024 * KSG_SD_NPT - 1) / (1024 * KSG_SD_NPT), 1);  // (k_static_dec_run's node tiles)
-    WinArgs AP = A;
-    AP.astride = 32;
-    AP.replay2 = r2 ? 1u : 0u;
-    __atomic_store_n(I.hverdict, 0u, __ATOMIC_RELEASE);
-    RunCtl RC{grid + I.run_need_extra, I.run_wait_us * 100u, 0, I.hverdict, I.run_spin};
-    if (overlap) {
-      RC.side_arrive = I.sready.p + sgroups;
-      RC.side_need = side_blocks;
-    }
-    bool sampled;
-    if (!sample_begin(I, s, true, sampled, err)) return false;
-    hipLaunchKernelGGL(kWindowRun[stat_run][I.eval_mode == 1], dim3(grid), dim3(KSG_WIN_THREADS), sizeof(WinLDS), s, C, I.F, AP, R,
-                       I.rsync.p, I.wsync.p, RC);
-    if (!sample_end(I, s, sampled, err)) return false;
-    HIPCHK(hipGetLastError());
-    if (overlap && I.static_beside_test == 1 && !issue_side()) return false;  // (tests: launched after the loop)
-    I.run_used = true;
-    const uint32_t v = wait_verdict(I, s, err);
-    if (overlap && I.static_beside_test == 2 && !issue_side()) return false;  // (tests: after the verdict)
-    if (v == 0u) return false;
-    if (v == 3u) {
-      I.lost = true;
-      err = "persistent launch: a gate never completed (blocks not co-resident?)";
-      return false;
-    }
-    if (v == 1u) {
-      I.win_runs++;
-      if (overlap) {  // (the run's last kernel after the side stream's records)
-        HIPCHK(hipStreamWaitEvent(s, I.sev_ready, 0));
-        I.static_overlaps++;
-      }
-      const int64_t L = nwin - 1;
-      hipLaunchKernelGGL(k_apply_pend, dim3(1), dim3(KSG_BATCH), 0, s, C, I.pend.p + (size_t)(L & 1) * KSG_BATCH,
-                         I.pend_n.p + (L & 1));
-      HIPCHK(hipEventRecord(I.ev1, s));
-      HIPCHK(hipGetLastError());
-      return true;
-    }
-    I.win_fallbacks++;  // v == 2: its blocks left untouched; the per-window launches
+  if (overlap) {
+    if (!I.sready.alloc(sgroups + 1, err) || !I.sd_pods.alloc((size_t)W.chunk * (sizeof(WcPod) / 8), err)) return false;
+    HIPCHK(hipMemsetAsync(I.sready.p, 0, (sgroups + 1) * sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(I.mpred.p, 0xFF, 2 * (size_t)count * sizeof(int64_t), s));
+    if (!I.sev_ready)
+      for (auto* e : {&I.sev_ready, &I.sev_free})
+        HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(I.sev_free, s));
+    HIPCHK(hipStreamWaitEvent(I.sstream, I.sev_free, 0));
+    if (!issue_side(0)) return false;
+  } else if (W.stat_run && !window_static(I, W, 0, StaticWhere{s}, err)) {  // (every record of the run)
+    return false;
+  }
+  if (!I.wsync.alloc(1, err) || !I.rsync.alloc(1, err) || !ensure_verdict(I, s, err)) return false;
+  HIPCHK(hipMemsetAsync(I.wsync.p, 0, sizeof(WinSync), s));
+  HIPCHK(hipMemsetAsync(I.rsync.p, 0, kRunSyncReset, s));
+  HIPCHK(hipMemsetAsync(I.arrive.p, 0, 2 * KSG_BATCH * 32 * sizeof(uint32_t), s));
+  // (every entry of both P lists starts unused: node -1, which the eval blocks
+  // read in place of a count; the per-window loop, on a fallback, goes by pend_n)
+  HIPCHK(hipMemsetAsync(I.pend.p, 0xFF, 2 * KSG_BATCH * sizeof(Pend), s));
+  WinRunArgs R{};
+  R.nwin = W.nwin; R.first = first; R.count = count; R.T = W.T;
+  R.tt_sz = (uint32_t)W.tt_sz; R.tf_sz = (uint32_t)W.tf_sz;
+  R.tile_top = I.tile_top.p; R.tfeas = I.tfeas.p; R.wrec = I.wrec.p;
+  R.pend = I.pend.p; R.pend_n = I.pend_n.p; R.arrive = I.arrive.p;
+  R.stamps = I.stamps_on ? I.stamps.p : nullptr; R.sready = overlap ? I.sready.p : nullptr;
+  R.sready_need = static_run_tiles(W.SN);
+  WinArgs AP = W.A;
+  AP.astride = 32; AP.replay2 = r2 ? 1u : 0u;
+  __atomic_store_n(I.hverdict, 0u, __ATOMIC_RELEASE);
+  RunCtl RC{grid + I.run_need_extra, I.run_wait_us * 100u, 0, I.hverdict, I.run_spin};
+  if (overlap) {
+    RC.side_arrive = I.sready.p + sgroups;
+    RC.side_need = std::min<uint32_t>(side_grid, static_run_tiles(W.SN) * sgroups);
+  }
+  bool sampled;
+  if (!sample_begin(I, s, true, sampled, err)) return false;
+  hipLaunchKernelGGL(kWindowRun[W.stat_run][I.eval_mode == 1], dim3(grid), dim3(KSG_WIN_THREADS), sizeof(WinLDS), s, W.C, I.F,
+                     AP, R, I.rsync.p, I.wsync.p, RC);
+  if (!sample_end(I, s, sampled, err)) return false;
+  HIPCHK(hipGetLastError());
+  if (!issue_side(1)) return false;
+  I.run_used = true;
+  const Verdict v = persistent_verdict(I, s, "persistent launch", err);
+  if (!issue_side(2)) return false;
+  if (v == Verdict::kError) return false;
+  if (v == Verdict::kRan) {
+    I.win_runs++;
+    if (overlap) I.static_overlaps++;
+    ran = true;
+  } else {
+    I.win_fallbacks++;  // its blocks left untouched; the per-window launches
     if (sampled) I.n_samples--;  // (the launch that left is not a sample)
-    // (the side kernel's records and maxima are rewritten by the per-window loop's
-    // k_static: it waits for the side kernel first)
-    if (overlap) HIPCHK(hipStreamWaitEvent(s, I.sev_ready, 0));
   }
-  for (int64_t j = -1; j < (int64_t)nwin; ++j) {
-    const int64_t E = j + 1, W = j;
-    A.ne = 0;
-    A.nw = 0;
-    A.stamps = A.estamps = nullptr;
-    A.tile_top = I.tile_top.p + (size_t)(E & 1) * tt_sz;
-    A.tile_feas = I.tfeas.p + (size_t)(E & 1) * tf_sz;
-    if (E < (int64_t)nwin) {
-      A.estamps = I.stamps_on ? I.stamps.p + (size_t)E * 32 : nullptr;
-      A.e0 = first + (uint32_t)E * KSG_BATCH;
-      A.ne = std::min<uint32_t>(KSG_BATCH, first + count - A.e0);
-      A.erec = sharded ? I.xsend.p : I.wrec.p + (size_t)(E & 1) * kRecBytes;
-    }
-    if (W >= 0) {
-      A.w0 = first + (uint32_t)W * KSG_BATCH;
-      A.nw = std::min<uint32_t>(KSG_BATCH, first + count - A.w0);
-      A.wrec = I.wrec.p + (size_t)(W & 1) * kRecBytes;
-      A.pnext = I.pend.p + (size_t)(W & 1) * KSG_BATCH;
-      A.pnext_n = I.pend_n.p + (W & 1);
-      A.stamps = I.stamps_on ? I.stamps.p + (size_t)W * 32 : nullptr;
-    }
-    const int64_t P = W - 1;  // P_{W-1}: the list the eval part overrides rows from, too
-    A.pprev = I.pend.p + (size_t)(P & 1) * KSG_BATCH;
-    A.pprev_n = I.pend_n.p + (P & 1);
-    const bool chunk_start = stat && A.ne && (A.e0 - first) % chunk == 0;
-    const uint32_t cidx = chunk_start ? (A.e0 - first) / chunk : 0;
-    if (chunk_start && !issue_static(cidx, s)) return false;
+  // (the run's last kernel, or the per-window loop's k_static, which rewrites the
+  // side kernel's records and maxima, after the side stream's records)
+  if (overlap) HIPCHK(hipStreamWaitEvent(s, I.sev_ready, 0));
+  return true;
+}
+
+// One k_window launch per window: launch j evaluates window j+1 and replays window j.
+// Each launch's arguments start from the shared ones: with ne == 0 it has no eval block
+// (the grid is 1 + ne * T), with nw == 0 block 0 returns at once: the other fields are never read.
+static bool window_per_launch(Engine::Impl& I, const WindowRun& W, std::string& err) {
+  hipStream_t s = W.s;
+  for (int64_t j = -1; j < (int64_t)W.nwin; ++j) {
+    const int64_t E = j + 1, Wn = j;
+    WinArgs a = W.A;
+    if (E < (int64_t)W.nwin)
+      win_eval_args(I, W, a, E, W.sharded ? I.xsend.p : I.wrec.p + (size_t)(E & 1) * kRecBytes, Wn - 1);
+    if (Wn >= 0) win_replay_args(I, W, a, Wn);
+    const bool chunk_start = W.stat && a.ne && (a.e0 - W.first) % W.chunk == 0;
+    if (chunk_start && !window_static(I, W, (a.e0 - W.first) / W.chunk, StaticWhere{s}, err)) return false;
     bool sampled;
-    if (!sample_begin(I, s, A.ne && A.nw, sampled, err)) return false;
-    dim3 grid(1 + A.ne * T);
-    const dim3 blk(KSG_WIN_THREADS);
-    hipLaunchKernelGGL(kWindow[stat][I.eval_mode == 1], grid, blk, sizeof(WinLDS), s, C, I.F, A);
+    if (!sample_begin(I, s, a.ne && a.nw, sampled, err)) return false;
+    hipLaunchKernelGGL(kWindow[W.stat][I.eval_mode == 1], dim3(1 + a.ne * W.T), dim3(KSG_WIN_THREADS), sizeof(WinLDS), s, W.C,
+                       I.F, a);
     if (!sample_end(I, s, sampled, err)) return false;
-    if (sharded && A.ne) {
+    if (W.sharded && a.ne) {
       if (!xgather(I, kXchgBytes, err)) return false;
-      hipLaunchKernelGGL(k_window_gmerge, dim3(A.ne), dim3(64), 0, s, I.xrecv.p, I.xranks, I.xrows.p, A.pprev,
-                         A.pprev_n, I.wrec.p + (size_t)(E & 1) * kRecBytes);
+      hipLaunchKernelGGL(k_window_gmerge, dim3(a.ne), dim3(64), 0, s, I.xrecv.p, I.xranks, I.xrows.p, a.pprev, a.pprev_n,
+                         I.wrec.p + (size_t)(E & 1) * kRecBytes);
     }
   }
-  if (nwin) {
-    const int64_t L = nwin - 1;
-    hipLaunchKernelGGL(k_apply_pend, dim3(1), dim3(KSG_BATCH), 0, s, C, I.pend.p + (size_t)(L & 1) * KSG_BATCH,
+  return true;
+}
+
+// The end of every path: the last window's pending rows written back on st (the
+// engine stream, or the split loop's replay stream, which the engine stream then joins).
+static bool window_tail(Engine::Impl& I, const WindowRun& W, hipStream_t st, std::string& err) {
+  if (W.nwin) {
+    const int64_t L = W.nwin - 1;
+    hipLaunchKernelGGL(k_apply_pend, dim3(1), dim3(KSG_BATCH), 0, st, W.C, I.pend.p + (size_t)(L & 1) * KSG_BATCH,
                        I.pend_n.p + (L & 1));
   }
-  HIPCHK(hipEventRecord(I.ev1, s));
+  if (st != W.s) {
+    HIPCHK(hipEventRecord(I.xjoin, st));  // everything after the run waits on the engine stream
+    HIPCHK(hipStreamWaitEvent(W.s, I.xjoin, 0));  // (the replay stream's last wait covers the exchange stream)
+  }
+  HIPCHK(hipEventRecord(I.ev1, W.s));
   HIPCHK(hipGetLastError());
   return true;
+}
+
+static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::string& err) {
+  if (I.R > 4) { err = "batch path supports at most 4 resource columns"; return false; }
+  WindowRun W{first, count, I.stream};
+  if (!window_setup(I, W, err)) return false;
+  hipStream_t tail = W.s;
+  if (W.sharded && !W.stat) {
+    if (!window_split(I, W, err)) return false;
+    tail = I.rstream;
+  } else {
+    bool ran = false;
+    if (W.persist && !window_persistent(I, W, ran, err)) return false;
+    if (!ran && !window_per_launch(I, W, err)) return false;
+  }
+  return window_tail(I, W, tail, err);
 }
 
 // The static record keeps the raw NodeAffinity score in 20 bits.
@@ -8042,8 +8054,6 @@ bool Engine::keep_outputs(uint32_t keep_first, uint32_t keep_n, std::string& err
          I.ktotal.alloc(N * keep_n, err);
 }
 
-static bool run_batches(Engine::Impl& I, uint32_t first, uint32_t count, std::string& err);
-
 // ---- A queue run outside the window path (Engine::run_queue): the static
 // chain for Taint / NodeAffinity profiles; otherwise per pod a persistent
 // segment, a table-chain cycle or a scanning-chain cycle.
@@ -8119,9 +8129,8 @@ static bool queue_static_chain(Engine::Impl& I, uint32_t first, uint32_t count, 
   for (uint32_t c0 = first; c0 < first + count; c0 += chunk) {
     const uint32_t cn = std::min(chunk, first + count - c0);
     HIPCHK(hipMemsetAsync(I.mpred.p, 0xFF, 2 * (size_t)cn * sizeof(int64_t), s));  // -1: no statically feasible node
-    const dim3 grid(std::max<uint32_t>((N + 256 * KSG_ST_NPT - 1) / (256 * KSG_ST_NPT), 1),
-                    (cn + KSG_ST_PODS - 1) / KSG_ST_PODS);
-    hipLaunchKernelGGL(k_static, grid, dim3(256), 0, s, C, I.F, I.progs.p, I.prog_off_d.p, c0, cn, I.stat.p, I.mpred.p, 0);
+    hipLaunchKernelGGL(k_static, static_grid(N, cn), dim3(256), 0, s, C, I.F, I.progs.p, I.prog_off_d.p, c0, cn, I.stat.p,
+                       I.mpred.p, 0);
     for (uint32_t j = c0; j < c0 + cn; ++j) {
       DevOut O{I.filter.p, I.score.p, I.total.p, I.sums.p + j, nullptr, commit ? 1 : 0, I.prow.p + j};
       kept_outputs(I, j, O);
@@ -8190,11 +8199,7 @@ static bool queue_setup(Engine::Impl& I, QueueRun& Q, std::string& err) {
   }
   Q.run_ok = Q.run_ok && I.run_on != 0 && I.cnblk + 1 <= I.run_cap && I.cnblk <= (uint32_t)kChain;  // (+1: the committer)
   if (Q.run_ok) {
-    if (!I.rsync.alloc(1, err) || !I.rgran.alloc(4 * kRunSlot, err)) return false;
-    if (!I.hverdict) {
-      HIPCHK(hipHostMalloc((void**)&I.hverdict, kVerdictBytes, hipHostMallocCoherent | hipHostMallocMapped));
-      HIPCHK(hipMemsetAsync(I.rsync.p, 0, sizeof(RunSync), s));  // (the sticky abort word starts clear)
-    }
+    if (!I.rsync.alloc(1, err) || !I.rgran.alloc(4 * kRunSlot, err) || !ensure_verdict(I, s, err)) return false;
   }
   return true;
 }
@@ -8243,14 +8248,9 @@ static bool queue_segment(Engine::Impl& I, QueueRun& Q, uint32_t j, uint32_t j1,
   // The handshake: the launch's blocks decide whether all of them are
   // resident before any state changes.  The host waits for that verdict (the
   // work queued before the segment runs first), then queues the rest.
-  const uint32_t v = wait_verdict(I, s, err);
-  if (v == 0u) return false;
-  if (v == 3u) {  // an earlier segment of this call aborted: the state is not valid
-    I.lost = true;
-    err = "persistent table chain: a gate never completed (blocks not co-resident?)";
-    return false;
-  }
-  if (v == 1u) {
+  const Verdict v = persistent_verdict(I, s, "persistent table chain", err);
+  if (v == Verdict::kError) return false;
+  if (v == Verdict::kRan) {
     I.path_pods[0] += j1 - j;
     I.path_pods[4] += j1 - j;
     I.path_pods[5]++;
@@ -8258,7 +8258,7 @@ static bool queue_segment(Engine::Impl& I, QueueRun& Q, uint32_t j, uint32_t j1,
     ran = true;
     return true;
   }
-  I.run_fallbacks++;  // v == 2
+  I.run_fallbacks++;
   Q.run_ok = false;
   return true;
 }

@@ -7,7 +7,7 @@ on that figure.  Per site, on the smallest cluster that reaches it: the number
 of samples (read off the site's gating condition), a positive average, and the
 path counters that show the intended path ran.
 
-The node-sharded sites (run_batches_split, the X1..X4 chains) need one process
+The node-sharded sites (window_split, the X1..X4 chains) need one process
 per rank, as tests/test_distributed.py starts them; they are not covered here.
 """
 import pytest

@@ -172,3 +172,23 @@ def test_static_side_kernel_late_or_absent(monkeypatch, mode):
     s.schedule()
     got = [(r.selected, r.feasible, r.status) for r in s.results()]
     assert got == [o.result(q) for q in range(len(got))]
+
+
+@pytest.mark.gpu
+def test_static_loop_not_resident_falls_back(monkeypatch):
+    """The side kernel issued before the loop, as by default, and a loop that then
+    leaves at its handshake (a grid that is never all resident, KSG_RUN_NORES=1): the
+    launch-per-window loop waits for the side kernel and rewrites its records and
+    maxima chunk by chunk.  Every pod equals the oracle's, no persistent run is
+    counted, the fallback is, and a second pass on the same context agrees too."""
+    monkeypatch.setenv("KSG_RUN_NORES", "1")
+    monkeypatch.setenv("KSG_RUN_WAIT_US", "300")
+    doc = g.generate(3, n_nodes=900, n_pods=500)
+    o, s = _compare(doc, every=13)
+    assert s.window_runs() == 0
+    assert s.run_fallbacks() >= 1
+    s.reset()
+    s.schedule()
+    got = [(r.selected, r.feasible, r.status) for r in s.results()]
+    assert got == [o.result(q) for q in range(len(got))]
+    assert s.window_runs() == 0
